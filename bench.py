@@ -28,11 +28,18 @@ draws a fresh rollout.  --pipeline (default): consecutive steps alternate betwee
 lanes and step k+1 waits only for step k's select, so its policy and select run beside step k's
 sort, fill and padding (one GPU: GFlowNet(pipeline=True); the columns split: two copies of its
 program with their own buffers); every step still does all of its work, with the same bits as
-steps run one after the other (tests/test_pipeline_gpu.py, tests/test_bench_dist_gpu.py).  The
-per-phase HIP-event timings come from an eager pass of the same step.  Prints ONE JSON line on
-rank 0.
+steps run one after the other (tests/test_pipeline_gpu.py, tests/test_bench_dist_gpu.py).  Prints
+ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c3] [--batch B]
+A plain run sets up, warms up, times the --steps steps and prints the headline line (value,
+ms_per_step, the last step's residuals).  --full adds everything that takes runs of its own: the
+eager pass with per-phase HIP-event timings, the per-kernel timer pass, the roofline objects, the
+generic residual leg, the steps without the M all_gather, the host issue times and the CPU
+baseline (--no-cpu-baseline leaves that one out).  --dump-outputs DIR writes what the last timed
+step computed (dump_outputs) so that two builds can be compared output for output.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c3] [--batch B] [--full]
+                  [--dump-outputs DIR]
 """
 import argparse
 import contextlib
@@ -323,6 +330,25 @@ def roofline_obj(kernel, nbytes, ms, traffic=None):
             "avg_launch_ms": ms}
 
 
+DUMP_SAMPLE = 1 << 20  # --dump-outputs: the elements kept of an output that has more
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as ``path/<name>.npy``, fp64 and integer arrays as float64 (exact:
+    the integers are action ids, counts and 32-bit bitmap words), the others as float32.  An array
+    of more than DUMP_SAMPLE elements is written as a fixed sample: DUMP_SAMPLE flat positions of
+    its row-major order drawn from numpy's default_rng(0), ascending, so the same positions in
+    every run with the same shapes (at most 8 arrays of 8 MB each)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t[torch.from_numpy(pos).to(t.device)]
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float64 if wide else np.float32))
+
+
 def launch_ranks(n: int) -> int:
     """`bench.py --gpus N` run directly: start the N ranks (one process per GPU) under
     torch.distributed.run on 127.0.0.1 as child processes and return their exit status.
@@ -385,6 +411,15 @@ def main():
     ap.add_argument("--dump", default=None,
                     help="write the last assembled step (Philox stream id, rewards of every candidate, the assembled "
                          "M) to this .pt file (rank 0; tests/test_bench_dist_gpu.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the eager pass with per-phase timings, the "
+                         "per-kernel timers and roofline objects, the generic residual leg, the steps without the M "
+                         "all_gather, the host issue times and the CPU baseline (a plain run only sets up, warms up, "
+                         "times --steps steps and prints value and ms_per_step)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (rank 0): rewards, "
+                         "residual, counts, the removal bitmap words, actions, fwd_probs and M (the assembled M of a "
+                         "split step as m_assembled); arrays of more than 2^20 elements as a fixed seeded sample")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -482,33 +517,40 @@ def main():
     with torch.no_grad():
         for _ in range(args.warmup):
             log = eager_step()
-        # eager pass with per-phase HIP events (on the stream the kernels run on)
-        kernels.TIMERS = {}
+        phase_ms, kernel_ms, dt_eager = {}, {}, 0.0
         k_eager = max(1, min(args.steps, 10))
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(k_eager):
-            log = eager_step()
-        barrier()
-        dt_eager = (time.perf_counter() - t0) / k_eager
-        phase_ms = {k: float(np.mean(kernels.timer_ms(k))) for k in kernels.TIMERS}
-        kernels.TIMERS = None
-        if dist_on:  # every rank's phase times, max over ranks (the collectives wait on the slowest rank)
-            names = sorted(phase_ms)
-            t = torch.tensor([phase_ms[k] for k in names], device=dev, dtype=torch.float64)
-            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-            phase_ms_max = dict(zip(names, t.tolist()))
-        kernel_ms = {}
-        if kernels.kernel_timers_available():
-            # single kernels inside the multi-kernel entry points (k_tile, k_sort2, the fill): HIP events
-            # around each launch on its stream, in a second eager pass (their records would add to the
-            # phase times above)
-            kernels.kernel_timer_arm(True)
+        if not args.full:
+            # the timed steps draw the same Philox streams with and without --full (the same rollouts timed
+            # and dumped, the step's cost depends on them): skip the ids of the passes left out
+            model.pipeline_join()
+            torch.cuda.synchronize()
+            model.rollouts += k_eager * (2 if kernels.kernel_timers_available() else 1)
+        else:
+            # eager pass with per-phase HIP events (on the stream the kernels run on)
+            kernels.TIMERS = {}
+            barrier()
+            t0 = time.perf_counter()
             for _ in range(k_eager):
                 log = eager_step()
             barrier()
-            kernels.kernel_timer_arm(False)
-            kernel_ms = {k: ms for k, (cnt, ms) in kernels.kernel_timer_read().items() if cnt > 0}
+            dt_eager = (time.perf_counter() - t0) / k_eager
+            phase_ms = {k: float(np.mean(kernels.timer_ms(k))) for k in kernels.TIMERS}
+            kernels.TIMERS = None
+            if dist_on:  # every rank's phase times, max over ranks (the collectives wait on the slowest rank)
+                names = sorted(phase_ms)
+                t = torch.tensor([phase_ms[k] for k in names], device=dev, dtype=torch.float64)
+                torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+                phase_ms_max = dict(zip(names, t.tolist()))
+            if kernels.kernel_timers_available():
+                # single kernels inside the multi-kernel entry points (k_tile, k_sort2, the fill): HIP events
+                # around each launch on its stream, in a second eager pass (their records would add to the
+                # phase times above)
+                kernels.kernel_timer_arm(True)
+                for _ in range(k_eager):
+                    log = eager_step()
+                barrier()
+                kernels.kernel_timer_arm(False)
+                kernel_ms = {k: ms for k, (cnt, ms) in kernels.kernel_timer_read().items() if cnt > 0}
 
         use_graph = not args.no_graph
         if use_graph:
@@ -699,7 +741,18 @@ def main():
             if gather is not None and args.assemble != "none":
                 dump["m_assembled"] = gather.result().cpu()
             torch.save(dump, args.dump)
-        if do_assemble[0]:  # the same steps without the M all_gather (reported apart)
+        if args.dump_outputs and rank == 0:  # what the last timed step's caller holds: its Log, residuals and M
+            last = use_graph and spg == 1
+            arrays = {"rewards": log.rewards if log.rewards_all is None else log.rewards_all,
+                      "residual": pstate["last"]["res"] if last else env.last_residual, "counts": log.counts,
+                      "removed": log.removed.view(torch.int32),
+                      "m": pstate["last"]["m"] if last else env.last_m}
+            if shard != "slices" or world == 1:  # (a slices split holds one slice of every trajectory per rank)
+                arrays["actions"], arrays["fwd_probs"] = log.actions, log.fwd_probs
+            if gather is not None and args.assemble != "none":
+                arrays["m_assembled"] = gather.result()
+            dump_outputs(args.dump_outputs, arrays)
+        if args.full and do_assemble[0]:  # the same steps without the M all_gather (reported apart)
             do_assemble[0] = False
             barrier()
             t0 = time.perf_counter()
@@ -709,7 +762,7 @@ def main():
             dt_noasm = (time.perf_counter() - t0) / args.steps
             do_assemble[0] = True
         host_us = None
-        if use_graph and dist_on:  # host issue time of each program entry (a pass after the timed steps)
+        if args.full and use_graph and dist_on:  # host issue time of each program entry (after the timed steps)
             host = {}
             for _ in range(k_eager):
                 step(host)
@@ -725,14 +778,7 @@ def main():
     res = env.last_residual.double().cpu().numpy()
     counts = log.counts.cpu().numpy()
 
-    if rank == 0:
-        # the fill kernel's own launch time (kernel timers), else its phase
-        fill_ms = kernel_ms.get("k_qr_solve" if args.fill == "qr" else "k_gram_fill",
-                                phase_ms.get("fill_residual", float("nan")))
-        fb = fill_bytes(env, B if shard == "columns" else bl)
-        if split:  # the rank's fill covers its own lines only (rank 0: the first shard)
-            fb *= (model.lines[1] - model.lines[0]) / n
-        gram_t = "f32" if env.gram is not None and env.gram.dtype == torch.float32 else "f64"
+    if rank == 0:  # the headline line of every run; --full adds its own measurements below
         workload = text + {
             "columns": (f", {bl} rollouts per GPU x {world} GPUs = B={B} candidates; columns of M sharded over the "
                         f"GPUs (256-line-aligned shards, fill + ||AM-I|| of every candidate per shard)" +
@@ -769,22 +815,39 @@ def main():
                                    f"{args.side[1]}-I||_F",
                        "N": n, "E": E, "global_batch": B, "rollouts_per_gpu": bl,
                        "parallelism": f"{shard} sharded x{world}"},
-            "value_without_assembly": B * n / dt_noasm,
-            "ms_per_step_without_assembly": dt_noasm * 1e3,
+            "full": args.full,
             "graph": use_graph,
             "steps_per_graph": spg,
             "pipeline": bool(args.pipeline and (not dist_on or split is not None)),
-            "ms_per_step_eager": dt_eager * 1e3,
             "final_residual_fro": float(res[0]),
             "final_residual_fro_mean": float(res.mean()),
             "removed_per_candidate_mean": float(counts.mean()),
+        }
+        if dist_on:
+            out["world_size"] = torch.distributed.get_world_size()
+            out["backend"] = torch.distributed.get_backend()
+            if args.backend == "nccl":
+                v = torch.cuda.nccl.version()
+                out["rccl_version"] = ".".join(str(x) for x in v) if isinstance(v, tuple) else str(v)
+    if rank == 0 and args.full:
+        # the fill kernel's own launch time (kernel timers), else its phase
+        fill_ms = kernel_ms.get("k_qr_solve" if args.fill == "qr" else "k_gram_fill",
+                                phase_ms.get("fill_residual", float("nan")))
+        fb = fill_bytes(env, B if shard == "columns" else bl)
+        if split:  # the rank's fill covers its own lines only (rank 0: the first shard)
+            fb *= (model.lines[1] - model.lines[0]) / n
+        gram_t = "f32" if env.gram is not None and env.gram.dtype == torch.float32 else "f64"
+        out.update({
+            "value_without_assembly": B * n / dt_noasm,
+            "ms_per_step_without_assembly": dt_noasm * 1e3,
+            "ms_per_step_eager": dt_eager * 1e3,
             "phases_ms": phase_ms,
             "roofline": roofline_obj(f"k_gram_fill<{env.pattern.width},{gram_t},LSQ> (LSQ fill of M + ||AM-I||^2; A "
                                      f"reaches it through the env-constant Gram cache)" if args.fill != "copy" else
                                      f"k_line{'_hash' if env.pattern.width > 7 else ''} (the reference's copy fill + "
                                      f"||{args.side[0]}{args.side[1]}-I||^2 of lines up to {env.pattern.width} wide)",
                                      fb, fill_ms, measured_traffic(args.config, bl)),
-        }
+        })
         if args.fill == "qr":  # the Householder-QR fill reads A itself: SURVEY §8(d)'s bytes are its bytes
             sbq = survey_fill_bytes(env, B if shard == "columns" else bl)
             if split:
@@ -866,15 +929,11 @@ def main():
             if host_us is not None:  # rank 0's host time to issue each graph replay / eager collective
                 out["host_issue_us"] = host_us
                 out["host_issue_us_total"] = sum(host_us.values())
-            out["world_size"] = torch.distributed.get_world_size()
-            out["backend"] = torch.distributed.get_backend()
-            if args.backend == "nccl":
-                v = torch.cuda.nccl.version()
-                out["rccl_version"] = ".".join(str(x) for x in v) if isinstance(v, tuple) else str(v)
         if not args.no_cpu_baseline and not dist_on:
             with torch.no_grad():
                 lg_host = model.forward_policy.logits(model.state_to_data(s0[:1])[0])[0].reshape(-1).cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(args.config, B, args.cpu_budget, lg_host, float(counts.mean()) + 1)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist_on:
         torch.distributed.destroy_process_group()

@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--config", default="c4")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--cmd", default="python bench.py --steps 10 --warmup 2 --no-cpu-baseline")
+    ap.add_argument("--cmd", default="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline")
     ap.add_argument("--fill", default="lsq", choices=["lsq", "qr"], help="the bench command's fill (its roofline kernel)")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)

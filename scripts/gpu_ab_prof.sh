@@ -14,7 +14,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
 for v in tree "$@"; do
   if [ "$v" = tree ]; then unset SPAI_LIB_VARIANT; else export SPAI_LIB_VARIANT=$v; fi
   O=gpurun_out/abp_${v}_$r
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o run -- python bench.py --config ${CFG:-c4} --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS} > $O.log 2>&1 || { tail -20 $O.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o run -- python bench.py --full --config ${CFG:-c4} --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS} > $O.log 2>&1 || { tail -20 $O.log; exit 1; }
   python - "$O" "$v" "${KERNELS}" <<'EOF'
 import csv, json, sys
 d, v, ks = sys.argv[1], sys.argv[2], sys.argv[3].split()

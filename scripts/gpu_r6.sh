@@ -35,19 +35,19 @@ for st in ${STEPS:-tests bench}; do
       TESTS= STEPS=30 ROUNDS=${ROUNDS:-3} bash scripts/gpu_ab.sh $VARIANTS || exit 1 ;;
     bench)
       for c in ${BENCH_CFGS:-c4}; do
-        timeout -k 10 400 python bench.py --config $c --steps 20 --warmup 3 ${BENCH_ARGS:---no-cpu-baseline} \
+        timeout -k 10 400 python bench.py --full --config $c --steps 20 --warmup 3 ${BENCH_ARGS:---no-cpu-baseline} \
           > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 1; }
         tail -1 $O/bench_$c.log | cut -c1-600
       done ;;
     prof)
       for c in ${PROF_CFGS:-c4}; do
         timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$c -o run -- \
-          python bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline > $O/prof_$c.log 2>&1 \
+          python bench.py --full --config $c --steps 10 --warmup 2 --no-cpu-baseline > $O/prof_$c.log 2>&1 \
           || { tail -20 $O/prof_$c.log; exit 1; }
       done ;;
     pmc)
       for c in ${PMC_CFGS:-c4}; do
-        PMC_TIMEOUT=300 bash scripts/pmc_kernels.sh $O/pmc_$c python bench.py --config $c --steps 10 --warmup 2 \
+        PMC_TIMEOUT=300 bash scripts/pmc_kernels.sh $O/pmc_$c python bench.py --full --config $c --steps 10 --warmup 2 \
           --no-cpu-baseline > $O/pmc_$c.log 2>&1 || { tail -20 $O/pmc_$c.log; exit 1; }
       done ;;
     qrbench)

@@ -9,7 +9,7 @@ mkdir -p $O
 timeout -k 10 300 python -u -m pytest tests/test_hip_parity.py tests/test_gmres.py -m gpu -x -q -k "residual or gmres or spmv" \
   --timeout 120 --timeout-method thread > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-timeout -k 10 300 python bench.py --config c3 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_c3.log 2>&1 || { tail -20 $O/bench_c3.log; exit 1; }
+timeout -k 10 300 python bench.py --full --config c3 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_c3.log 2>&1 || { tail -20 $O/bench_c3.log; exit 1; }
 tail -1 $O/bench_c3.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('c3', d['ms_per_step'], json.dumps(d['roofline_residual']))"
 timeout -k 10 300 python scripts/resid_bench.py --config c3 > $O/resid_c3.log 2>&1 || { tail -20 $O/resid_c3.log; exit 1; }
 tail -1 $O/resid_c3.log

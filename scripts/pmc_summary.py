@@ -37,7 +37,7 @@ if os.path.exists(stats):
         summary["kernels"][k]["calls"] = int(r["Calls"])
     with open(os.path.join(out_dir, f"kernel_stats_{tag}.md"), "w") as f:
         f.write(f"# rocprofv3 --kernel-trace --stats ({tag})\n\nCommand: `rocprofv3 --kernel-trace --stats "
-                f"--output-format csv -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline` on one MI355X.\n\n")
+                f"--output-format csv -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline` on one MI355X.\n\n")
         f.write("\n".join(lines) + "\n")
     with open(os.path.join(out_dir, f"kernel_stats_{tag}.csv"), "w") as f:
         f.write(open(stats).read())

@@ -27,7 +27,7 @@ def test_bench_columns_step_under_rccl_matches_one_gpu(tmp_path, fill):
     dump = tmp_path / f"dist_{fill}.pt"
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--gpus", "1", "--dist", "--backend",
-           "nccl", "--fill", fill, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--dump", str(dump)]
+           "nccl", "--fill", fill, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--dump", str(dump)]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     # the bench line explains the multi-GPU step: the collective phases (max over ranks), the group, RCCL

@@ -5,6 +5,7 @@ field/symmetry, multi-chunk sizes, whitespace variants and malformed input at 1,
 threads.  Each run must exit cleanly with no sanitizer report and agree with
 scipy.io.mmread (the reference's reader, gflownet/utils.py:54-63): dims, entry count and a
 fixed-order checksum of the (row, col, value) arrays."""
+import ctypes
 import os
 import shutil
 import subprocess
@@ -39,9 +40,19 @@ def exes(tmp_path_factory):
     return out
 
 
+def _no_aslr():
+    """In the child, before exec: personality(ADDR_NO_RANDOMIZE).  g++ 11's ThreadSanitizer runtime
+    accepts only its fixed address ranges and exits at start-up ("FATAL: ThreadSanitizer: unexpected
+    memory mapping", status 66) when the kernel randomises mappings past them (vm.mmap_rnd_bits = 32);
+    without randomisation the executable and its libraries load at the addresses it expects.  The
+    reader runs under the sanitizers exactly as before."""
+    ctypes.CDLL(None).personality(0x0040000)
+
+
 def run(exe, path, threads):
     env = dict(os.environ, **ENV)
-    r = subprocess.run([exe, path, str(threads)], capture_output=True, text=True, env=env, timeout=120)
+    r = subprocess.run([exe, path, str(threads)], capture_output=True, text=True, env=env, timeout=120,
+                       preexec_fn=_no_aslr)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
     return r.stdout.split()
