@@ -21,7 +21,7 @@ if os.environ.get("SPAI_LIB_VARIANT"):  # A/B timing of kernel variants built un
 SPAI_OK, SPAI_ERR_INVALID, SPAI_ERR_HIP, SPAI_ERR_UNSUPPORTED = 0, 1, 2, 3
 FILL_COPY, FILL_LSQ = 0, 1  # (the Householder-QR fill has its own entry point)
 DTYPE_F32, DTYPE_F64 = 0, 1
-ABI_VERSION = 20
+ABI_VERSION = 21
 RES2_LIMBS = 8  # SPAI_RES2_LIMBS
 
 _c_i32, _c_i64, _c_u64, _c_sz, _c_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_void_p
@@ -112,6 +112,13 @@ SIGNATURES = {
                                             _c_p]),
     "spai_fill_lines_gram_dict": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32,
                                                  _c_p, _c_i32, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_sz, _c_p]),
+    "spai_qr_wide_limits": (ctypes.c_int, [_c_p, _c_p, _c_p]),
+    "spai_qr_wide_max_rows": (ctypes.c_int, [_c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_p]),
+    "spai_qr_wide_cache_bytes": (_c_sz, [_c_i32, _c_i32]),
+    "spai_qr_wide_factor": (ctypes.c_int, [_c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_i32, _c_i32, _c_p, _c_sz,
+                                           _c_p]),
+    "spai_fill_lines_qr_wide": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_sz, _c_i32, _c_p,
+                                               _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_sz, _c_p]),
 }
 
 _lib = None

@@ -233,10 +233,13 @@ def solve_with_gmres(A, b, M=None, *, verbose: bool = True, device=None, maxiter
     return x.cpu().numpy(), residuals, len(residuals), elapsed
 
 
-def spai_power_pattern(A, power: int = 1, device=None):
+def spai_power_pattern(A, power: int = 1, device=None, fill: str | None = None):
     """The power-pattern SPAI baseline: M with the sparsity of A^power,
     each column the least-squares solution of min ||A m_j - e_j|| (the env's LSQ fill, AM side,
-    nothing removed).  Returns M as a sparse COO tensor on the device (A's dtype)."""
+    nothing removed).  ``fill``: "lsq" (normal equations of the Gram cache) or "qr" (Householder
+    QR); None = "lsq" where the Gram fill applies (pattern columns <= 13 entries over A columns
+    <= 7) and "qr" otherwise (up to 32 / 32: A^2 of a 3-D stencil, 9- and 27-point stencils).
+    Returns M as a sparse COO tensor on the device (A's dtype)."""
     import scipy.sparse as sp
 
     from .preconditioner import PreconditionerEnv
@@ -247,11 +250,14 @@ def spai_power_pattern(A, power: int = 1, device=None):
     Pk = P
     for _ in range(power - 1):
         Pk = Pk @ P
+    if fill is None:  # widths of the AM side's lines: the columns
+        w, wa = int(np.diff(Pk.tocsc().indptr).max()), int(np.diff(Acsr.tocsc().indptr).max())
+        fill = "lsq" if w <= 13 and wa <= 7 else "qr"
     Pk = Pk.tocoo()
     pat = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([Pk.row, Pk.col]).astype(np.int64)),
                                   torch.ones(Pk.nnz, dtype=torch.float32), (n, n))
     orig = torch.sparse_coo_tensor(torch.stack([rows, cols]), vals, (n, n))
-    env = PreconditionerEnv(n, pat, orig, side="AM", fill="lsq", keep_m=True, device=device)
+    env = PreconditionerEnv(n, pat, orig, side="AM", fill=fill, keep_m=True, device=device)
     words = (env.init_nnz + 31) // 32
     removed = torch.zeros(1, words, dtype=torch.int32, device=env.device)
     counts = torch.zeros(1, dtype=torch.int32, device=env.device)

@@ -431,24 +431,59 @@ def fill_residual_gram(pattern: Lines, gram, removed: torch.Tensor, lsq: bool, l
     return (lb if limbs else res2), m
 
 
+def qr_wide_limits() -> tuple:
+    """(max pattern width, max A-line width, max row union) of the wide QR fill (spai_qr_wide_limits);
+    no GPU needed."""
+    w, wa, rows = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(_l().spai_qr_wide_limits(ctypes.byref(w), ctypes.byref(wa), ctypes.byref(rows)), "spai_qr_wide_limits")
+    return w.value, wa.value, rows.value
+
+
 def qr_max_rows(pattern: Lines, a_lines: Lines) -> int:
     """Largest row union |I| over the lines (the dense block A[I, slots] the QR fill factors);
-    one host sync (once per env).  spai_qr_max_rows."""
+    one host sync (once per env).  spai_qr_max_rows where a narrow width class fits, else
+    spai_qr_wide_max_rows (NotImplementedError past the wide limits)."""
     _lib.require_device(pattern.idx)
     out = torch.empty(1, dtype=torch.int32, device=pattern.idx.device)
-    _lib.check(_l().spai_qr_max_rows(pattern.n, pattern.width, _lib.ptr(pattern.idx), a_lines.width,
-                                     _lib.ptr(a_lines.idx), _lib.ptr(out), _lib.stream_ptr(pattern.idx.device)),
-               "spai_qr_max_rows")
+    wide = qr_class(pattern.width, a_lines.width) not in (5, 7, 13)
+    fn = _l().spai_qr_wide_max_rows if wide else _l().spai_qr_max_rows
+    _lib.check(fn(pattern.n, pattern.width, _lib.ptr(pattern.idx), a_lines.width, _lib.ptr(a_lines.idx),
+                  _lib.ptr(out), _lib.stream_ptr(pattern.idx.device)),
+               "spai_qr_wide_max_rows" if wide else "spai_qr_max_rows")
     return int(out.item())
 
 
-def qr_cache(pattern: Lines, a_lines: Lines, max_rows: int):
+class WideRCache:
+    """The wide QR fill's R cache (spai_qr_wide_factor): ``tensor`` holds one record of
+    W (W + 1) / 2 + W + 1 fp64 values per line, line-major, for pattern width ``W``.  Accepted as
+    ``rcache`` wherever the narrow cache is; it has no dictionary form."""
+
+    def __init__(self, tensor: torch.Tensor, W: int):
+        self.tensor, self.W = tensor, W
+
+    @property
+    def nbytes(self) -> int:
+        return self.tensor.numel() * self.tensor.element_size()
+
+
+def qr_cache(pattern: Lines, a_lines: Lines, max_rows: int, wide: bool | None = None):
     """The R cache of the QR fill (spai_qr_factor): per line the Householder R of its full block
     A[I, slots], Q^T e_l and the tail, fp64, built once per env (pattern widths <= 13 over A
-    widths <= 7; the 13-wide solve re-reads its line's R per sample at one wave per SIMD).  None
-    for wider lines (the fused spai_fill_lines_qr runs instead)."""
+    widths <= 7; the 13-wide solve re-reads its line's R per sample at one wave per SIMD).
+    ``wide``: None = the wide cache (a WideRCache, spai_qr_wide_factor: widths up to
+    qr_wide_limits()) only when no narrow class fits; True forces it on a narrow pattern."""
     _lib.require_device(pattern.idx)
     lib = _l()
+    if wide is None:
+        wide = qr_class(pattern.width, a_lines.width) not in (5, 7, 13)
+    if wide:
+        nb = lib.spai_qr_wide_cache_bytes(pattern.n, pattern.width)
+        rc = torch.empty(max(nb, 8) // 8, dtype=torch.float64, device=pattern.idx.device)
+        av = narrow_values(a_lines)
+        _lib.check(lib.spai_qr_wide_factor(pattern.n, pattern.width, _lib.ptr(pattern.idx), a_lines.width,
+                                           _lib.ptr(a_lines.idx), _lib.ptr(av), _DT[av.dtype], max_rows, _lib.ptr(rc),
+                                           nb, _lib.stream_ptr(pattern.idx.device)), "spai_qr_wide_factor")
+        return WideRCache(rc, pattern.width)
     nb = lib.spai_qr_cache_bytes(pattern.n, pattern.width, a_lines.width)
     if nb == 0 or not (pattern.width <= 13 and a_lines.width <= 7):
         return None
@@ -478,15 +513,20 @@ class CacheDict:
 
 
 QrDict = CacheDict  # (the R cache's dictionary)
+QR_WIDE_CLASS = 32  # qr_class of lines past the narrow classes (not a compiled lane-per-line width)
 
 
 def qr_class(W: int, WA: int) -> int:
-    """Width class of the QR fill (qr.hip qr_class): 5, 7 or 13."""
+    """Width class of the QR fill (qr.hip qr_class): 5, 7 or 13; QR_WIDE_CLASS for wider lines
+    within qr_wide_limits() (the wavefront-per-line kernels of qr_wide.hip), 0 past them."""
     if W <= 5 and WA <= 5:
         return 5
     if W <= 7 and WA <= 7:
         return 7
-    return 13
+    if W <= 13 and WA <= 7:
+        return 13
+    mw, mwa, _ = qr_wide_limits()
+    return QR_WIDE_CLASS if W <= mw and WA <= mwa else 0
 
 
 def qr_cache_q(wc: int) -> int:
@@ -500,8 +540,8 @@ def qr_table_offset(n_lines: int, B: int) -> int:
 
 
 def cache_nbytes(cache) -> int:
-    """Bytes one rollout's fill reads of a per-line cache (full tensor or CacheDict)."""
-    return cache.nbytes if isinstance(cache, CacheDict) else cache.numel() * cache.element_size()
+    """Bytes one rollout's fill reads of a per-line cache (full tensor, CacheDict or WideRCache)."""
+    return cache.nbytes if isinstance(cache, (CacheDict, WideRCache)) else cache.numel() * cache.element_size()
 
 
 rcache_nbytes = cache_nbytes
@@ -535,6 +575,19 @@ def qr_dict(rcache: torch.Tensor, pattern: Lines, a_lines: Lines | None = None, 
 def _fill_lines_qr(pattern: Lines, a_lines: Lines, max_rows: int, removed: torch.Tensor, line_begin: int,
                    line_end: int, m, m_dtype, word_base: int, ws, rcache=None):
     B, words = removed.shape
+    if rcache is None and qr_class(pattern.width, a_lines.width) == QR_WIDE_CLASS:
+        rcache = qr_cache(pattern, a_lines, max_rows, wide=True)  # no fused wide kernel: a scratch cache per call
+    if isinstance(rcache, WideRCache):  # the wavefront-per-line solve (qr_wide.hip)
+        if rcache.W != pattern.width:
+            raise ValueError(f"the wide R cache was factored for width {rcache.W}, the pattern has {pattern.width}")
+        rc = rcache.tensor
+        with _timed("fill_residual"):  # the fill kernel alone
+            st = _l().spai_fill_lines_qr_wide(pattern.n, line_begin, line_end, pattern.width, _lib.ptr(pattern.act),
+                                              _lib.ptr(rc), rc.numel() * 8, B, _lib.ptr(removed), words, word_base,
+                                              _lib.ptr(m), _DT[m_dtype], _lib.ptr(ws), ws.numel(),
+                                              _lib.stream_ptr(removed.device))
+        _lib.check(st, "spai_fill_lines_qr_wide")
+        return
     if rcache is not None:  # phase 2 only, from the env's R cache (full, or its dictionary)
         if isinstance(rcache, QrDict):
             nq = qr_cache_q(qr_class(pattern.width, a_lines.width))

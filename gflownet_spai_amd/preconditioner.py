@@ -16,16 +16,26 @@ Extensions (keyword-only, defaults = reference behaviour):
   side="MA" | "AM"    which residual: ||M A - I|| (reference) or ||A M - I|| (column SPAI)
   fill="copy" | "lsq" | "qr"  M = copied pattern values (reference) or per-line least squares:
                       "lsq" by the normal equations of the Gram cache (the bench path), "qr" by
-                      Householder QR of each line's dense block A[I, J] (spai_fill_lines_qr)
+                      Householder QR of each line's dense block A[I, J] (spai_fill_lines_qr): any
+                      pattern up to 32 slots per line over A lines up to 32 entries with row
+                      unions |I| <= 256 (kernels.qr_wide_limits()); past the lane-per-line width
+                      classes (W <= 13 over WA <= 7) the wavefront-per-line kernels run
+                      (spai_qr_wide_factor + spai_fill_lines_qr_wide); wider still:
+                      NotImplementedError at construction.  "lsq" stops at 13 / 7
   keep_m=False        keep the last batch's M values (LSQ) in ``self.last_m``
   rcache=True         fill="qr": factor every line's full block once per env (spai_qr_factor) and
                       solve each rollout's masked problems from that R cache; False: the fused
-                      kernel refactors every call
+                      kernel refactors every call (the wide kernels have no fused form: they
+                      factor into a scratch cache on every call)
+  qr_wide=None        fill="qr": None = the wide kernels only when no narrow width class fits
+                      (every narrow configuration runs the kernels it always ran); True forces
+                      them on a narrow pattern (the tests compare the two paths there)
   cache_dict=True     keep the Gram / R cache as its dictionary (kernels.CacheDict,
                       spai_line_cache_dict) when at most a quarter of the lines have distinct
                       entries — a stencil's interior lines share one: the same bits from fewer
                       HBM bytes (and two waves per SIMD for the 8-13-wide Gram fill; the
-                      5/7-wide Gram fill keeps its full cache: no gain measured)
+                      5/7-wide Gram fill keeps its full cache: no gain measured); the wide R
+                      cache has no dictionary form and is kept whole
 Documented deviations: alpha is taken from the ``alpha`` argument (the reference reads
 the never-set ``self.alpha``, preconditioner.py:163); fp64 original matrices are
 accepted (the reference raises in torch.mm, utils.py:350); a raw COO pattern with
@@ -62,7 +72,7 @@ def _default_device():
 class PreconditionerEnv(Env):
     def __init__(self, matrix_size: int, initial_matrix: Tensor, original_matrix: Tensor, *, side: str = "MA",
                  fill: str = "copy", keep_m: bool = False, device=None, compact_gram: bool = True,
-                 rcache: bool = True, cache_dict: bool = True):
+                 rcache: bool = True, cache_dict: bool = True, qr_wide: bool | None = None):
         if side not in ("MA", "AM"):
             raise ValueError("side must be 'MA' or 'AM'")
         if fill not in ("copy", "lsq", "qr"):
@@ -103,7 +113,21 @@ class PreconditionerEnv(Env):
         # the factorisation of the FULL block is sample-independent, so it is done once here into the
         # R cache (rcache=False: refactor every call, the fused kernel)
         self.qr_rows = kernels.qr_max_rows(self.pattern, self.a_lines) if fill == "qr" else None
-        self.rcache = (kernels.qr_cache(self.pattern, self.a_lines, self.qr_rows)
+        # lines past the narrow width classes (or qr_wide=True) run the wavefront-per-line kernels
+        self.qr_wide = False
+        if fill == "qr":
+            wc = kernels.qr_class(self.pattern.width, self.a_lines.width)
+            narrow = wc in (5, 7, 13) and self.qr_rows <= {5: 32, 7: 64, 13: 96}[wc]  # (qr.hip qr_rows_cap)
+            self.qr_wide = (not narrow) if qr_wide is None else bool(qr_wide)
+            if not narrow and not self.qr_wide:
+                raise ValueError("qr_wide=False needs a pattern of a narrow width class (W <= 13 over WA <= 7)")
+            if self.qr_wide:
+                mw, mwa, mrows = kernels.qr_wide_limits()
+                if self.pattern.width > mw or self.a_lines.width > mwa or self.qr_rows > mrows:
+                    raise NotImplementedError(
+                        f"fill='qr': pattern width {self.pattern.width}, A width {self.a_lines.width}, row union "
+                        f"{self.qr_rows} above the compiled limits {mw} / {mwa} / {mrows}")
+        self.rcache = (kernels.qr_cache(self.pattern, self.a_lines, self.qr_rows, wide=self.qr_wide)
                        if fill == "qr" and rcache else None)
         if self.gram is not None and compact_gram:
             # integer stencils (and any A whose G, c are fp32-exact): the same cache in fp32
@@ -115,6 +139,8 @@ class PreconditionerEnv(Env):
             for name in ("gram", "rcache"):
                 full = getattr(self, name)
                 if full is None or (name == "gram" and self.pattern.width <= 7):
+                    continue
+                if isinstance(full, kernels.WideRCache):  # line-major records: no dictionary form
                     continue
                 d = kernels.cache_dict(full, matrix_size)
                 if d is not None:
@@ -159,7 +185,7 @@ class PreconditionerEnv(Env):
         pat = self.pattern if pattern is None else pattern
         if self.fill == "qr":
             res2, m = kernels.fill_residual_qr(pat, self.a_lines, self.qr_rows, removed, line_begin, line_end,
-                                               rcache=self.rcache, **kw)
+                                               rcache=self._rc(), **kw)
         elif self.gram is not None:
             res2, m = kernels.fill_residual_gram(pat, self.gram, removed, self._lsq, line_begin, line_end, **kw)
         else:
@@ -172,6 +198,13 @@ class PreconditionerEnv(Env):
                  and line_begin == 0 and (line_end is None or line_end == self.matrix_size))
         self.last_removed = removed if whole else None
         return res2
+
+    def _rc(self):
+        """The R cache a QR fill call reads: the env's, or with rcache=False on the wide kernels
+        (which have no fused form) one factored for this call."""
+        if self.rcache is None and self.qr_wide:
+            return kernels.qr_cache(self.pattern, self.a_lines, self.qr_rows, wide=True)
+        return self.rcache
 
     def pack_plan(self, world: int):
         """The columns split's bitmap exchange plan for ``world`` ranks (distributed.PackPlan; one
@@ -210,7 +243,7 @@ class PreconditionerEnv(Env):
         if self.fill == "qr":
             self.last_residual, reward, self.last_reward32, m = kernels.fill_rewards_qr(
                 self.pattern, self.a_lines, self.qr_rows, removed, counts, self.init_nnz, self._r0, self.orig_flops,
-                alpha, store_m=self.keep_m, m_dtype=self.a_lines.val.dtype, rcache=self.rcache)
+                alpha, store_m=self.keep_m, m_dtype=self.a_lines.val.dtype, rcache=self._rc())
         else:
             self.last_residual, reward, self.last_reward32, m = kernels.fill_rewards_gram(
                 self.pattern, self.gram, removed, self.fill == "lsq", counts, self.init_nnz, self._r0,

@@ -342,6 +342,39 @@ int spai_fill_lines_qr_cached(int32_t n, int32_t line_begin, int32_t line_end, i
                               int32_t entries, int32_t B, const uint32_t* removed, int32_t words, int32_t word_base,
                               void* m_out, int32_t m_dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- the QR fill for wide lines (ABI 21)
+ * The same least-squares fill for patterns past the three width classes above: W <= 32 slots per
+ * line over A lines of WA <= 32 entries, row unions |I| <= 256 (spai_qr_wide_limits returns the
+ * compiled limits; past them every call below returns SPAI_ERR_UNSUPPORTED).  Same two phases, a
+ * wavefront per line instead of a lane per line:
+ *   spai_qr_wide_max_rows  the largest |I| over the lines (as spai_qr_max_rows, any W, WA <= 32);
+ *   spai_qr_wide_factor    once per env: the Householder QR of every line's full block, one
+ *     workgroup per line (64 threads when max_rows <= 64, else 256; thread = row of the block),
+ *     into the wide R cache, line-major: line l's record is NQ = W (W + 1) / 2 + W + 1 doubles at
+ *     rcache[l * NQ] = R packed upper triangular (row i at i W - i (i - 1) / 2, entries i .. W - 1),
+ *     (Q^T e_l)[0 .. W), then the tail ||(Q^T e_l)[W ..]||^2 (+ 1 when l is not in I; NaN when the
+ *     line has more than max_rows rows).  W is the pattern's width itself (no width classes);
+ *     spai_qr_wide_cache_bytes(n, W) = 8 n NQ, 0 for n <= 0 or W outside 1 .. 32;
+ *   spai_fill_lines_qr_wide  per rollout, from that cache and the pattern's action ids: one
+ *     half-wave per (line, sample), lane q holding column q of R, the masked re-triangularisation
+ *     and rank floor of spai_fill_lines_qr_cached (the floor 1e-24 sum_i R_ip^2 in fp64), then
+ *     back-substitution; the same outputs, bitmap window convention (word_base), workspace
+ *     (spai_fill_workspace_bytes) and partial layout as the other fills, so spai_fill_reduce /
+ *     spai_fill_reduce_rewards follow it and 256-line-aligned shards sum to one launch's bits.
+ * Narrow patterns are accepted too (the tests compare the two paths there).  No cache dictionary.
+ * No reference counterpart (utils.py:331-353 copies the pattern values). */
+int spai_qr_wide_limits(int32_t* max_w, int32_t* max_wa, int32_t* max_rows);
+int spai_qr_wide_max_rows(int32_t n, int32_t W, const int32_t* pat_idx, int32_t WA, const int32_t* a_idx,
+                          int32_t* max_rows, void* stream);
+size_t spai_qr_wide_cache_bytes(int32_t n, int32_t W);
+int spai_qr_wide_factor(int32_t n, int32_t W, const int32_t* pat_idx, int32_t WA, const int32_t* a_idx,
+                        const void* a_val, int32_t a_dtype, int32_t max_rows, double* rcache, size_t rcache_bytes,
+                        void* stream);
+int spai_fill_lines_qr_wide(int32_t n, int32_t line_begin, int32_t line_end, int32_t W, const int32_t* pat_act,
+                            const double* rcache, size_t rcache_bytes, int32_t B, const uint32_t* removed,
+                            int32_t words, int32_t word_base, void* m_out, int32_t m_dtype, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- cache dictionaries
  * The dictionary of a per-line cache in the blocked layout of spai_qr_factor / spai_gram_build
  * (value q of line j at ((j / 64) * nq + q) * 64 + j % 64, elem_bytes 8 or 4): its distinct line
