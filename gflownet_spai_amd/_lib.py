@@ -21,7 +21,7 @@ if os.environ.get("SPAI_LIB_VARIANT"):  # A/B timing of kernel variants built un
 SPAI_OK, SPAI_ERR_INVALID, SPAI_ERR_HIP, SPAI_ERR_UNSUPPORTED = 0, 1, 2, 3
 FILL_COPY, FILL_LSQ = 0, 1  # (the Householder-QR fill has its own entry point)
 DTYPE_F32, DTYPE_F64 = 0, 1
-ABI_VERSION = 21
+ABI_VERSION = 22
 RES2_LIMBS = 8  # SPAI_RES2_LIMBS
 
 _c_i32, _c_i64, _c_u64, _c_sz, _c_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_void_p
@@ -86,6 +86,15 @@ SIGNATURES = {
     "spai_policy_backward": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                             _c_p, _c_p, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
     "spai_ell_spmv":(ctypes.c_int, [_c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_p, _c_p, _c_p]),
+    "spai_ell_spmv_batched": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_p, _c_i64, _c_p, _c_i32, _c_i64, _c_p, _c_p,
+                                             _c_p, _c_p, _c_p]),
+    "spai_gmres_workspace_bytes": (_c_sz, [_c_i32, _c_i32, _c_i32]),
+    "spai_gmres_batched_init": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_double, ctypes.c_double,
+                                               _c_i32, _c_p, _c_i64, _c_p, _c_i32, _c_i64, _c_p, _c_p, _c_p, _c_p,
+                                               _c_p, _c_sz, _c_p]),
+    "spai_gmres_batched_cycle": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_i32,
+                                                _c_p, _c_i64, _c_p, _c_i32, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                _c_sz, _c_p]),
     "spai_mtx_header": (ctypes.c_int, [ctypes.c_char_p, _c_p, _c_p]),
     "spai_mtx_read": (ctypes.c_int, [ctypes.c_char_p, _c_p, _c_p, _c_p, _c_i64, _c_i32, _c_p]),
     "spai_lstm_states_floats": (_c_sz, [_c_i32, _c_i32, _c_i32]),

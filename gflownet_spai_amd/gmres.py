@@ -13,10 +13,17 @@ and axpys of the Gram-Schmidt are device ops; only the (restart+1)-sized Hessenb
 crosses to the host once per inner iteration, where the rotations run in fp64 exactly as scipy
 runs them.  Preconditioners: None, a sparse matrix (SPAI M: applied on the GPU) or a host
 callable / LinearOperator (e.g. the spilu baseline: applied on the host, copied each way).
+
+``gmres_batched`` / ``evaluate_candidates`` run the same algorithm for B samples in lock step
+entirely on the device (csrc/krylov_batched.hip): one shared A, a different M per sample
+(``BatchedOperator``: the env's ``last_m`` read in place, or a list of sparse matrices), classical
+Gram-Schmidt with one re-orthogonalisation instead of the modified one, 8 launches per inner
+iteration whatever B and the iteration, and one host read per restart cycle.
 """
 from __future__ import annotations
 
 import time
+from dataclasses import dataclass
 from typing import Callable
 
 import numpy as np
@@ -263,3 +270,219 @@ def spai_power_pattern(A, power: int = 1, device=None, fill: str | None = None):
     counts = torch.zeros(1, dtype=torch.int32, device=env.device)
     env.rewards_from_removed(removed, counts, torch.tensor(0.5))
     return env.assemble(0)
+
+
+# ---------------------------------------------------------------------- batched, on the device
+MAX_RESTART = 64  # krylov_batched.hip kMaxRestart
+
+
+def row_view(lines: Lines):
+    """Row gather view of column lines: (idx [n, Wr] int32 column of each row slot, -1 padded;
+    src [n, Wr] int32 flat position line * W + slot of that entry in the column lines, 0 in the
+    padding).  With it M = values[src] over idx is applied row by row (no scatter); depends on
+    the pattern only.  Works on any device."""
+    n, W = lines.n, lines.width
+    flat = lines.idx.reshape(-1).long()
+    pos = torch.nonzero(flat >= 0).reshape(-1)
+    rows, cols = flat[pos], pos // W
+    order = torch.argsort(rows * n + cols, stable=True)
+    rows, cols, pos = rows[order], cols[order], pos[order]
+    counts = torch.bincount(rows, minlength=n)
+    wr = max(int(counts.max()) if pos.numel() else 0, 1)
+    start = torch.cumsum(counts, 0) - counts
+    slot = torch.arange(pos.numel(), device=flat.device) - start[rows]
+    idx = torch.full((n * wr,), -1, dtype=torch.int32, device=flat.device)
+    src = torch.zeros(n * wr, dtype=torch.int32, device=flat.device)
+    idx[rows * wr + slot] = cols.to(torch.int32)
+    src[rows * wr + slot] = pos.to(torch.int32)
+    return idx.view(n, wr), src.view(n, wr)
+
+
+def _keep_mask(env) -> torch.Tensor:
+    """[B, n, W] bool: the pattern slots the last batch's removal bitmaps keep (assemble's rule)."""
+    if env.last_removed is None:
+        raise ValueError("no removal bitmaps: run update / rewards_from_removed first or pass removed")
+    act = env.pattern.act.long()
+    a = act.clamp(min=0)
+    bits = env.last_removed.to(env.pattern.act.device)
+    return (act >= 0).unsqueeze(0) & (((bits[:, a >> 5] >> (a & 31).unsqueeze(0)) & 1) == 0)
+
+
+class BatchedOperator:
+    """y[b] = Op_b x[b] for B samples on the GPU (spai_ell_spmv_batched): row-ELL ``idx`` shared
+    ([n, W]) or per sample ([B, n, W]); values shared (``val_bstride`` 0) or per sample, read in
+    place or through the int32 indirection ``src`` [n, W] (a column-oriented pattern's values)."""
+
+    def __init__(self, n: int, B: int, idx: torch.Tensor, val: torch.Tensor, *, val_bstride: int,
+                 src: torch.Tensor | None = None, nnz=None):
+        if idx.dtype != torch.int32 or val.dtype not in (torch.float32, torch.float64):
+            raise ValueError("BatchedOperator takes int32 indices and fp32 / fp64 values")
+        if src is not None and (idx.dim() != 2 or src.shape != idx.shape or src.dtype != torch.int32):
+            raise ValueError("src needs a shared [n, W] pattern and its shape")
+        _lib.require_device(idx)
+        self.n, self.B, self.width = n, B, int(idx.shape[-1])
+        self.idx, self.val, self.src = idx.contiguous(), val.contiguous(), None if src is None else src.contiguous()
+        self.idx_bstride = 0 if idx.dim() == 2 else n * self.width
+        self.val_bstride = int(val_bstride)
+        self.nnz = nnz
+        self.device = idx.device
+        self.shape = (B, n, n)
+
+    @classmethod
+    def identity(cls, n: int, B: int, device) -> "BatchedOperator":
+        idx = torch.arange(n, dtype=torch.int32, device=device).view(n, 1)
+        return cls(n, B, idx, torch.ones(n, 1, dtype=torch.float64, device=device), val_bstride=0)
+
+    @classmethod
+    def from_matrices(cls, mats, n: int | None = None, device=None) -> "BatchedOperator":
+        """One operator per entry of ``mats`` (scipy / torch sparse; None = the identity, stored
+        as a diagonal), padded to the widest row."""
+        mats = list(mats)
+        if not mats:
+            raise ValueError("from_matrices needs at least one matrix")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        coos = [None if m is None else _coo_of(m) for m in mats]
+        sizes = {c[3] for c in coos if c is not None} | ({int(n)} if n is not None else set())
+        if len(sizes) != 1:
+            raise ValueError(f"from_matrices needs one matrix size, got {sorted(sizes)}")
+        n = sizes.pop()
+        vd = torch.float64 if any(c is None or c[2].dtype == torch.float64 for c in coos) else torch.float32
+        lines = []
+        for c in coos:
+            if c is None:
+                d = torch.arange(n)
+                c = (d, d, torch.ones(n, dtype=vd), n)
+            lines.append(build_lines(c[0], c[1], c[2], n, "row", dev, vd))
+        W = max(L.width for L in lines)
+        pad = torch.nn.functional.pad
+        idx = torch.stack([pad(L.idx, (0, W - L.width), value=-1) for L in lines])
+        val = torch.stack([pad(L.val, (0, W - L.width)) for L in lines])
+        nnz = [int((L.idx >= 0).sum()) for L in lines]
+        return cls(n, len(lines), idx, val, val_bstride=n * W, nnz=nnz)
+
+    @classmethod
+    def from_env(cls, env) -> "BatchedOperator":
+        """The M of every sample of the env's last batch, read where the fill left it
+        (``env.last_m``; fill="copy": the pattern's values masked by ``env.last_removed``)."""
+        if env._lsq and env.last_m is None:
+            raise ValueError("construct with keep_m=True to keep M")
+        keep = _keep_mask(env)
+        pat = env.pattern
+        n, W, B = pat.n, pat.width, keep.shape[0]
+        if env._lsq:
+            if env.last_m.shape[0] != B:
+                raise ValueError("env.last_m and env.last_removed are of different batches")
+            val = env.last_m.reshape(B, n * W)
+        else:
+            val = torch.where(keep, pat.val.unsqueeze(0), torch.zeros((), dtype=pat.val.dtype, device=pat.val.device))
+            val = val.reshape(B, n * W)
+        nnz = keep.reshape(B, -1).sum(1)
+        if pat.orient == "row":
+            return cls(n, B, pat.idx, val, val_bstride=n * W, nnz=nnz)
+        if getattr(env, "_row_view", None) is None:  # env-constant: all samples share the pattern
+            env._row_view = row_view(pat)
+        idx, src = env._row_view
+        return cls(n, B, idx, val, val_bstride=n * W, src=src, nnz=nnz)
+
+    def _args(self):
+        dt = _lib.DTYPE_F64 if self.val.dtype == torch.float64 else _lib.DTYPE_F32
+        return (self.width, _lib.ptr(self.idx), self.idx_bstride, _lib.ptr(self.val), dt, self.val_bstride,
+                _lib.ptr(self.src))
+
+    def matvec_into(self, x: torch.Tensor, y: torch.Tensor, active: torch.Tensor | None = None) -> torch.Tensor:
+        for t in (x, y):
+            if t.dtype != torch.float64 or not t.is_contiguous() or t.device != self.device or \
+                    tuple(t.shape) != (self.B, self.n):
+                raise ValueError("BatchedOperator.matvec_into takes contiguous fp64 [B, n] tensors on its device")
+        if active is not None and (active.dtype != torch.int32 or active.numel() != self.B or
+                                   active.device != self.device or not active.is_contiguous()):
+            raise ValueError("active must be a contiguous int32 [B] tensor on the operator's device")
+        W, idx, ibs, val, dt, vbs, src = self._args()
+        st = kernels._l().spai_ell_spmv_batched(self.n, W, self.B, idx, ibs, val, dt, vbs, src, _lib.ptr(x),
+                                                _lib.ptr(y), _lib.ptr(active), _lib.stream_ptr(self.device))
+        _lib.check(st, "spai_ell_spmv_batched")
+        return y
+
+    def matvec(self, x: torch.Tensor) -> torch.Tensor:
+        return self.matvec_into(x, torch.empty_like(x))
+
+
+@dataclass
+class BatchedGmresResult:
+    x: torch.Tensor          # [B, n] fp64, on the device
+    info: np.ndarray         # [B] int64: 0 = converged, maxiter otherwise (scipy's exit code)
+    iterations: np.ndarray   # [B] int64 inner iterations
+    residuals: list          # B lists: the legacy callback's values, one per inner iteration
+    nnz: np.ndarray | None = None  # evaluate_candidates: nnz(M) per sample
+
+
+def gmres_batched(A, b, M=None, *, rtol=1e-5, atol=0.0, restart=None, maxiter=None, device=None) -> BatchedGmresResult:
+    """``_gmres`` with a callback, for B samples at once on the device: A as for ``gmres`` (shared),
+    b [n] (shared) or [B, n], M None | BatchedOperator | list of sparse matrices / None (identity).
+    x0 = 0, left preconditioning, ``maxiter`` counts inner iterations, a zero right-hand side gives
+    x = 0 and info 0 for that sample.  Host-callable preconditioners are not batched."""
+    Aop = A if isinstance(A, DeviceOperator) else DeviceOperator(A, device=device)
+    dev, n = Aop.device, Aop.n
+    if M is not None and not isinstance(M, (BatchedOperator, list, tuple)):
+        raise TypeError("gmres_batched takes M = None, a BatchedOperator or a list of sparse matrices; a host "
+                        "callable / LinearOperator (or one matrix) goes through solve_with_gmres")
+    if isinstance(M, (list, tuple)):
+        if any(m is not None and (callable(m) or hasattr(m, "matvec")) and not hasattr(m, "tocoo") and
+               not isinstance(m, torch.Tensor) for m in M):
+            raise TypeError("gmres_batched cannot batch host callables / LinearOperators: use solve_with_gmres")
+        M = BatchedOperator.from_matrices(M, n=n, device=dev)
+    bt = torch.as_tensor(np.asarray(b, dtype=np.float64) if not isinstance(b, torch.Tensor) else b, dtype=torch.float64)
+    if bt.dim() not in (1, 2) or bt.shape[-1] != n:
+        raise ValueError(f"Shape mismatch: A is {Aop.shape}, but b is {tuple(bt.shape)}")
+    B = M.B if M is not None else (bt.shape[0] if bt.dim() == 2 else 1)
+    if M is None:
+        M = BatchedOperator.identity(n, B, dev)
+    if M.n != n or M.device != dev:
+        raise ValueError("M and A differ in size or device")
+    if bt.dim() == 2 and bt.shape[0] != B:
+        raise ValueError(f"b has {bt.shape[0]} right-hand sides for {B} preconditioners")
+    rhs = (bt.to(dev).expand(B, n) if bt.dim() == 1 else bt.to(dev)).contiguous()
+    if atol is None or atol < 0:
+        raise ValueError("atol must be a real, non-negative number")
+    if maxiter is None:
+        maxiter = n * 10
+    if maxiter < 1:
+        raise ValueError("maxiter must be at least 1")
+    restart = min(20 if restart is None else int(restart), n)
+    lib = kernels._l()
+    nbytes = lib.spai_gmres_workspace_bytes(n, B, min(restart, MAX_RESTART))
+    ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    x = torch.empty(B, n, dtype=torch.float64, device=dev)
+    report = torch.zeros(B, 8 + restart, dtype=torch.int64, device=dev)
+    stream = _lib.stream_ptr(dev)
+    margs = M._args()
+    tail = (_lib.ptr(rhs), _lib.ptr(x), _lib.ptr(report), _lib.ptr(ws), ws.numel(), stream)
+    _lib.check(lib.spai_gmres_batched_init(n, B, restart, int(maxiter), float(rtol), float(atol), *margs, *tail),
+               "spai_gmres_batched_init")
+    L = Aop.lines
+    adt = _lib.DTYPE_F64 if L.val.dtype == torch.float64 else _lib.DTYPE_F32
+    residuals = [[] for _ in range(B)]
+    done = np.zeros(B, dtype=np.int64)
+    rep = report.cpu()  # the one host read per cycle
+    while bool(rep[:, 0].any()):
+        _lib.check(lib.spai_gmres_batched_cycle(n, B, restart, int(maxiter), L.width, _lib.ptr(L.idx), _lib.ptr(L.val),
+                                                adt, *margs, *tail), "spai_gmres_batched_cycle")
+        rep = report.cpu()
+        its = rep[:, 2].numpy()
+        hist = rep[:, 8:].view(torch.float64)
+        for s in np.nonzero(its > done)[0]:
+            residuals[s].extend(hist[s, :its[s] - done[s]].tolist())
+        done = its.copy()
+    return BatchedGmresResult(x, rep[:, 3].numpy().copy(), done, residuals)
+
+
+def evaluate_candidates(env, b, **kw) -> BatchedGmresResult:
+    """GMRES on the env's A for every candidate M of the env's last batch at once (after
+    ``sample_states`` / ``rewards_from_removed`` with ``keep_m=True``): ``gmres_batched`` with
+    ``BatchedOperator.from_env(env)``, plus each sample's nnz(M)."""
+    M = BatchedOperator.from_env(env)
+    if getattr(env, "_a_operator", None) is None:
+        env._a_operator = DeviceOperator(env.original_matrix, device=env.device)
+    res = gmres_batched(env._a_operator, b, M, **kw)
+    res.nnz = M.nnz.cpu().numpy()
+    return res

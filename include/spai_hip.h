@@ -523,6 +523,57 @@ int spai_rewards(const double* res2, const int32_t* removed_counts, int32_t B, i
 int spai_ell_spmv(int32_t n, int32_t W, const int32_t* idx, const void* val, int32_t val_dtype, const double* x,
                   double* y, void* stream);
 
+/* ---------------------------------------------------------------- batched Krylov evaluation (ABI 22)
+ * GMRES(restart) for B samples in lock step: one shared A, a different M and right-hand side per
+ * sample (gflownet_spai_amd/gmres.py gmres_batched; per sample the arithmetic of gmres._gmres =
+ * scipy.sparse.linalg.gmres with the legacy callback, x0 = 0, left preconditioning, the Gram-Schmidt
+ * being classical with one re-orthogonalisation).  Every vector is fp64, [B][n].  All reductions
+ * are per-block partials summed in a fixed order with a row partition that depends on n only (no
+ * floating-point atomics): sample b's bits do not depend on B or on the other samples.
+ *
+ * spai_ell_spmv_batched: y[b] = Op_b x[b] for every sample with active[b] != 0 (active NULL: all;
+ * y[b] of an inactive sample is not written).  Op_b is row-ELL, width W (any W >= 1), one thread per
+ * row, fp64 fma in slot order as spai_ell_spmv:
+ *   idx   [n][W] (idx_bstride 0: one pattern for all samples) or [B][n][W] (idx_bstride n W),
+ *         -1 = padding;
+ *   val   fp32 or fp64 (val_dtype), sample b's values start at val + b val_bstride elements
+ *         (0 = shared values);
+ *   src   NULL: the value of row slot (i, s) is val_b[i W + s]; else int32 [n][W] (shared pattern
+ *         only, every entry a valid index, padding slots included) and it is val_b[src[i W + s]]:
+ *         a column-oriented pattern's values ([B][n][W] in line order, 0 where not kept, as
+ *         m_out above) applied as a row gather. */
+int spai_ell_spmv_batched(int32_t n, int32_t W, int32_t B, const int32_t* idx, int64_t idx_bstride, const void* val,
+                          int32_t val_dtype, int64_t val_bstride, const int32_t* src, const double* x, double* y,
+                          const int32_t* active, void* stream);
+/* Workspace of the two calls below (the Krylov bases [B][restart + 1][n], three vectors [B][n],
+ * the partials and the per-sample small state); 0 for a bad shape. */
+size_t spai_gmres_workspace_bytes(int32_t n, int32_t B, int32_t restart);
+/* spai_gmres_batched_init: x = 0, r = rhs, ||rhs[b]||, ||M_b rhs[b]||, the tolerances
+ * (atol_b = max(atol, rtol ||rhs[b]||)) and the report; samples with a zero right-hand side (x = 0,
+ * info 0) or ||rhs[b]|| < atol_b are finished here.  spai_gmres_batched_cycle: one restart cycle of
+ * every unfinished sample (at most `restart` inner iterations of 8 launches each, whatever B and the
+ * iteration; then x += V y, r = rhs - A x and the exit rules), stream-ordered without a host
+ * synchronisation; blocks of a sample that has left the cycle return at once.  The caller reads
+ * `report` after each call and stops when no sample is alive.  Both calls take the same workspace
+ * (state lives in it between them), rhs, x, report and M.
+ *   restart 1 .. 64 (above: SPAI_ERR_UNSUPPORTED), maxiter >= 1 counts inner iterations;
+ *   A       a_idx / a_val [n][a_W] row-ELL, shared by all samples (a_val_dtype);
+ *   M       as the operator of spai_ell_spmv_batched (m_src may be NULL; no other pointer may);
+ *   rhs, x  [B][n] fp64;
+ *   report  [B][8 + restart] 8-byte words per sample: int64 alive, (in-cycle) active, iterations,
+ *           info (0 or maxiter), columns of the last cycle, breakdown, capped, 0; then fp64
+ *           presid / ||rhs[b]|| of the inner iterations of the LAST cycle (iterations - previous
+ *           iterations of them are valid). */
+int spai_gmres_batched_init(int32_t n, int32_t B, int32_t restart, int32_t maxiter, double rtol, double atol,
+                            int32_t m_W, const int32_t* m_idx, int64_t m_idx_bstride, const void* m_val,
+                            int32_t m_val_dtype, int64_t m_val_bstride, const int32_t* m_src, const double* rhs,
+                            double* x, int64_t* report, void* workspace, size_t workspace_bytes, void* stream);
+int spai_gmres_batched_cycle(int32_t n, int32_t B, int32_t restart, int32_t maxiter, int32_t a_W,
+                             const int32_t* a_idx, const void* a_val, int32_t a_val_dtype, int32_t m_W,
+                             const int32_t* m_idx, int64_t m_idx_bstride, const void* m_val, int32_t m_val_dtype,
+                             int64_t m_val_bstride, const int32_t* m_src, const double* rhs, double* x,
+                             int64_t* report, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- Matrix Market ingest (host)
  * gflownet/utils.py:54-63 market_matrix_to_sparse_tensor / GFlowNet100.py:44-46 load_mtx_file:
  * scipy.io.mmread(path).tocoo().  Coordinate format; field real / integer / pattern; symmetry
