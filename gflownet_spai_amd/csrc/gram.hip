@@ -17,6 +17,7 @@
 // is 1 - c^T m* = 1 - sum_k y_k^2 / D_k from the factorisation; it equals the residual of
 // the stored (rounded) values up to d^T G d, d = rounding of m (<= 1e-14 relative for fp32 M).
 #include "spai_device.h"
+#include "spai_fill.h"
 #include "spai_status.h"
 #include "spai_timer.h"
 
@@ -25,9 +26,7 @@ namespace {
 
 constexpr int kNT = 256;
 constexpr int kChunk = 8;  // samples per LDS residual chunk of the fill kernel
-#ifndef FILL_WPE5
-#define FILL_WPE5 4  // waves/SIMD of the 5-wide fill (7-wide: 2, no spills)
-#endif
+constexpr int kFillWpe5 = 4;  // waves/SIMD of the 5-wide fill (7-wide: 2, no spills)
 
 __host__ __device__ constexpr int tri(int w) { return w * (w + 1) / 2; }
 
@@ -35,13 +34,6 @@ __host__ __device__ constexpr int tri(int w) { return w * (w + 1) / 2; }
 template <int W>
 __device__ __forceinline__ constexpr int gidx(int p, int q) {
   return p * W - p * (p - 1) / 2 + (q - p);
-}
-
-// 1/x to ~1 ulp: hardware reciprocal + one Newton step (the pivots are positive, normal).
-__device__ __forceinline__ double fast_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  const double e = fma(-x, r, 1.0);
-  return fma(r, e, r);
 }
 
 template <int W, int WA, typename TA>
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(kNT) void k_gram_build(int32_t n, int32_t wrt, int3
 // kDict: gram is the cache's dictionary (spai_line_cache_dict: distinct entries of T + W values,
 // contiguous) and line_entry[j] names line j's entry; else the full cache, 64 lines interleaved.
 template <int W, typename TM, bool LSQ, typename GT, bool kDict>
-__global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? FILL_WPE5 : 2))) void k_gram_fill(int32_t n, int32_t line_begin, int32_t line_end, int32_t wrt,
+__global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? kFillWpe5 : 2))) void k_gram_fill(int32_t n, int32_t line_begin, int32_t line_end, int32_t wrt,
                                                    const int32_t* __restrict__ pat_act,
                                                    const float* __restrict__ pat_val,
                                                    const GT* __restrict__ gram,
@@ -113,11 +105,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? FI
                                                    double* __restrict__ partials) {
   constexpr int T = tri(W);
   __shared__ double s_r2[kChunk][kNT];
-#ifdef FILL_BLOCK_M
-  __shared__ __attribute__((aligned(16))) TM s_m[2][kNT * W];
-#else
-  __shared__ __attribute__((aligned(16))) TM s_m[1][kNT * W];  // per-wave regions
-#endif
+  __shared__ __attribute__((aligned(16))) TM s_m[kNT * W];  // per-wave regions (stage_m_wave)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int lb = blockIdx.x;
   const int j = line_begin + lb * kNT + t;
@@ -125,7 +113,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? FI
   const int64_t nloc = line_end - line_begin;
   const int jj = valid ? j : line_begin;  // clamped: loads stay in bounds
 
-  int act[W];
+  int act[W];  // (its own load form, not load_line_acts: the helper's clamped loads change an instance's SGPR count)
   float val[W];
   const int32_t* pa = pat_act + (int64_t)jj * wrt;
 #pragma unroll
@@ -142,7 +130,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? FI
   for (int p = 0; p < W; ++p) c[p] = (double)gp[(T + p) * kStride];
   int wofs[W];  // bitmap word offsets / bit positions of the slots
 #pragma unroll
-  for (int p = 0; p < W; ++p) wofs[p] = act[p] >= 0 ? (act[p] >> 5) - word_base : 0;  // row-relative
+  for (int p = 0; p < W; ++p) wofs[p] = slot_word(act[p], word_base);
   const int nvl = min(kNT, line_end - (line_begin + lb * kNT));  // valid lines of the block
 
   // the bitmap words of the next sample are loaded while the current one is solved
@@ -157,7 +145,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? FI
       const int b = b0 + s;
       bool keep[W];
 #pragma unroll
-      for (int p = 0; p < W; ++p) keep[p] = act[p] >= 0 && !((wd[p] >> (act[p] & 31)) & 1u);
+      for (int p = 0; p < W; ++p) keep[p] = slot_kept(act[p], wd[p]);
       if (b + 1 < B) {
         const uint32_t* rn = removed + (int64_t)(b + 1) * words;
 #pragma unroll
@@ -169,12 +157,6 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? FI
       if constexpr (!LSQ) {
 #pragma unroll
         for (int p = 0; p < W; ++p) mr[p] = keep[p] ? (double)val[p] : 0.0;
-#ifdef FILL_NOCOMPUTE  // diagnostic variant: memory traffic without the solve
-      } else if (true) {
-#pragma unroll
-        for (int p = 0; p < W; ++p) mr[p] = keep[p] ? c[p] * G[gidx<W>(p, p)] : 0.0;
-        r2ls = mr[0] + mr[W - 1];
-#endif
       } else {
         // masked LDL^T of the normal equations. A removed slot k only gets iD[k] = 0: every
         // L[.][k] = EL[.][k] * iD[k] is then exactly 0, so the kept unknowns see exactly the
@@ -189,7 +171,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? FI
           double dk = gkk;
 #pragma unroll
           for (int q = 0; q < k; ++q) dk -= L[k][q] * EL[k][q];
-          iD[k] = (keep[k] && dk > 1e-13 * gkk) ? fast_rcp(dk) : 0.0;
+          iD[k] = (keep[k] && dk > 1e-13 * gkk) ? rcp_newton(dk) : 0.0;
 #pragma unroll
           for (int i = k + 1; i < W; ++i) {
             double v = G[gidx<W>(k, i)];
@@ -216,44 +198,8 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? FI
           mr[k] = v;
         }
       }
-#ifdef FILL_BLOCK_M  // A/B: M staged per block (a block barrier per sample)
-      if (m_out != nullptr) {
-        // M through LDS (double-buffered per sample): the block's lines of one sample are one
-        // contiguous run of nvl * wrt values, written with 16-byte stores
-        TM* sm = s_m[b & 1];
-        if (valid) {
-#pragma unroll
-          for (int p = 0; p < W; ++p)
-            if (p < wrt) sm[t * wrt + p] = (TM)mr[p];
-        }
-        __syncthreads();
-        TM* dst = m_out + ((int64_t)b * nloc + (int64_t)lb * kNT) * wrt;
-        const int ne = nvl * wrt;
-        constexpr int V = 16 / sizeof(TM);
-        int e0 = 0;
-        if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-          for (int e = t; e < ne / V; e += kNT)
-            nt_store(reinterpret_cast<nt_u4*>(dst) + e, reinterpret_cast<const nt_u4*>(sm)[e]);
-          e0 = ne / V * V;
-        }
-        for (int e = e0 + t; e < ne; e += kNT) nt_store(dst + e, sm[e]);
-      }
-#else
-      {  // M staged per WAVE (its 64 lines are one contiguous run of M): no block barrier per sample
-        const int wv = __builtin_amdgcn_readfirstlane(wave);  // wave-uniform: scalar offsets
-      TM* sm = s_m[0] + wv * 64 * W;
-        if (valid) {
-#pragma unroll
-          for (int p = 0; p < W; ++p)
-            if (p < wrt) sm[lane * wrt + p] = (TM)mr[p];
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int nw = min(max(nvl - wv * 64, 0), 64);
-        store_m_block<64, W, TM>(m_out ? m_out + ((int64_t)b * nloc + (int64_t)lb * kNT + wv * 64) * wrt : nullptr,
-                                 sm, nw * wrt, lane);
-        __builtin_amdgcn_wave_barrier();
-      }
-#endif
+      // M staged per wave, not per block: no block barrier per sample
+      stage_m_wave<W, TM>(s_m, mr, valid, lane, wave, wrt, nvl, m_out, b, nloc, lb);
       double r2 = 0.0;
       if (valid) {
         if constexpr (LSQ) {
@@ -271,8 +217,10 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? FI
       }
       s_r2[s][t] = r2;
     }
+    // chunk_block_sums(s_r2, lane, wave, nb, b0, partials, lb) written out, operation for operation:
+    // through the helper the 5-wide LSQ instances take one VGPR more (the same IR in another block order)
     __syncthreads();
-    for (int s = wave; s < nb; s += kNT / 64) {  // fixed-order per-sample block sums
+    for (int s = wave; s < nb; s += kNT / 64) {
       double acc = 0.0;
 #pragma unroll
       for (int q = 0; q < kNT / 64; ++q) acc += s_r2[s][q * 64 + lane];
@@ -310,7 +258,7 @@ __device__ __forceinline__ double wide_lsq_solve(double (&a)[tri(W)], double (&y
       d -= l * a[gidx<W>(q, k)];
       a[gidx<W>(q, k)] = l;
     }
-    a[gidx<W>(k, k)] = (((keep >> k) & 1u) && d > 1e-13 * gkk) ? fast_rcp(d) : 0.0;
+    a[gidx<W>(k, k)] = (((keep >> k) & 1u) && d > 1e-13 * gkk) ? rcp_newton(d) : 0.0;
   }
 #pragma unroll
   for (int k = 0; k < W; ++k) {  // forward substitution in place (y[q < k] are final)
@@ -351,15 +299,10 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(kDict ? 2 :
   constexpr int T = tri(W);
   static_assert(W <= 32, "keep mask is one 32-bit word");
   // per-sample line residuals of a chunk of kChunk samples (summed after the chunk: one barrier
-  // pair per chunk, not per sample) and M staged through two LDS buffers (sample b writes buffer
-  // b & 1 while sample b - 1's stores may still read the other)
-  // (kDict: ONE M buffer, a barrier before it is rewritten: <= 80 KB of LDS, two blocks per CU)
+  // pair per chunk, not per sample) and M staged per wave (stage_m_wave: one buffer, no block
+  // barrier per sample; <= 80 KB of LDS, two blocks per CU for kDict)
   __shared__ double s_r2[kChunk][kNT];
-#ifdef FILL_BLOCK_M
-  __shared__ __attribute__((aligned(16))) TM s_m[kDict ? 1 : 2][kNT * W];
-#else
-  __shared__ __attribute__((aligned(16))) TM s_m[1][kNT * W];  // per-wave regions
-#endif
+  __shared__ __attribute__((aligned(16))) TM s_m[kNT * W];
   __shared__ int32_t s_act[W][kNT];  // action ids of the slots (LDS, not registers: G needs them)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int lb = blockIdx.x;
@@ -368,11 +311,10 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(kDict ? 2 :
   const int64_t nloc = line_end - line_begin;
   const int jj = valid ? j : line_begin;
   {
-    int av[W];  // every load issued before any is used (no branch per slot)
+    int act[W];
+    load_line_acts<W>(pat_act, jj, wrt, valid, act);
 #pragma unroll
-    for (int p = 0; p < W; ++p) av[p] = pat_act[(int64_t)jj * wrt + min(p, wrt - 1)];
-#pragma unroll
-    for (int p = 0; p < W; ++p) s_act[p][t] = (valid && p < wrt) ? av[p] : -1;
+    for (int p = 0; p < W; ++p) s_act[p][t] = act[p];
   }
   constexpr int kStride = kDict ? 1 : 64;
   const GT* gp = kDict ? gram + (int64_t)line_entry[jj] * (T + W) : gram + (int64_t)(jj >> 6) * (T + W) * 64 + (jj & 63);
@@ -446,45 +388,10 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(kDict ? 2 :
       }
     }
     s_r2[b % kChunk][t] = valid ? r2 : 0.0;
-#ifdef FILL_BLOCK_M
-    {  // M (no branch on m_out: store_m_block drops every store when it is null)
-      TM* sm = s_m[kDict ? 0 : (b & 1)];
-      if constexpr (kDict) __syncthreads();  // the previous sample's stores have read the buffer
-      if (valid) {
-#pragma unroll
-        for (int p = 0; p < W; ++p)
-          if (p < wrt) sm[t * wrt + p] = (TM)y[p];
-      }
-      __syncthreads();
-      store_m_block<kNT, W, TM>(m_out ? m_out + ((int64_t)b * nloc + (int64_t)lb * kNT) * wrt : nullptr, sm, nvl * wrt);
-    }
-#else
-    {  // M staged per WAVE (its 64 lines are one contiguous run of M): no block barrier per sample
-      const int wv = __builtin_amdgcn_readfirstlane(wave);  // wave-uniform: scalar offsets
-      TM* sm = s_m[0] + wv * 64 * W;
-      if (valid) {
-#pragma unroll
-        for (int p = 0; p < W; ++p)
-          if (p < wrt) sm[lane * wrt + p] = (TM)y[p];
-      }
-      __builtin_amdgcn_wave_barrier();
-      const int nw = min(max(nvl - wv * 64, 0), 64);
-      store_m_block<64, W, TM>(m_out ? m_out + ((int64_t)b * nloc + (int64_t)lb * kNT + wv * 64) * wrt : nullptr,
-                               sm, nw * wrt, lane);
-      __builtin_amdgcn_wave_barrier();
-    }
-#endif
+    stage_m_wave<W, TM>(s_m, y, valid, lane, wave, wrt, nvl, m_out, b, nloc, lb);
     if (b % kChunk == kChunk - 1 || b == B - 1) {  // the chunk's fixed-order block sums
       const int c0 = b - b % kChunk, nb = b - c0 + 1;
-      __syncthreads();
-      for (int u = wave; u < nb; u += kNT / 64) {
-        double acc = 0.0;
-#pragma unroll
-        for (int q = 0; q < kNT / 64; ++q) acc += s_r2[u][q * 64 + lane];
-        acc = wave_sum(acc);
-        if (lane == 0) partials[(int64_t)(c0 + u) * gridDim.x + lb] = acc;
-      }
-      __syncthreads();
+      chunk_block_sums<kNT>(s_r2, lane, wave, nb, c0, partials, lb);
     }
   }
 }
@@ -597,18 +504,14 @@ static int fill_lines_gram(int32_t fill_mode, int32_t n, int32_t line_begin, int
                            void* stream) {
   SPAI_CHECK_ARG(fill_mode == SPAI_FILL_COPY || fill_mode == SPAI_FILL_LSQ,
                  "spai_fill_lines_gram(_dict): bad fill_mode %d", fill_mode);
-  SPAI_CHECK_ARG(m_dtype == SPAI_DTYPE_F32 || m_dtype == SPAI_DTYPE_F64, "spai_fill_lines_gram(_dict): bad m_dtype");
-  SPAI_CHECK_ARG(n >= 1 && line_begin >= 0 && line_end >= line_begin && line_end <= n && W >= 1 && B >= 1 &&
-                     words >= 1 && word_base >= 0,
-                 "spai_fill_lines_gram(_dict): bad shape");
-  SPAI_CHECK_ARG(workspace != nullptr, "spai_fill_lines_gram(_dict): null workspace");
-  SPAI_CHECK_ARG(fill_mode != SPAI_FILL_COPY || m_dtype == SPAI_DTYPE_F32,
+  SPAI_CHECK_ARG(fill_mode != SPAI_FILL_COPY || m_dtype != SPAI_DTYPE_F64,
                  "spai_fill_lines_gram(_dict): copy fill stores fp32 values (utils.py:350)");
+  int32_t nparts;
+  const int st = check_fill_lines("spai_fill_lines_gram(_dict)", n, line_begin, line_end, W, B, words, word_base, true,
+                                  m_dtype, workspace, workspace_bytes,
+                                  pat_act && gram && removed && (fill_mode == SPAI_FILL_LSQ || pat_val), &nparts);
+  if (st != SPAI_OK || nparts == 0) return st;
   hipStream_t s = (hipStream_t)stream;
-  const int32_t nl = line_end - line_begin;
-  if (nl == 0) return SPAI_OK;
-  SPAI_CHECK_ARG(pat_act && gram && removed && (fill_mode == SPAI_FILL_LSQ || pat_val),
-                 "spai_fill_lines_gram(_dict): null input");
   const int wc = gram_width(W);
   if (wc == 0) {
     set_error("spai_fill_lines_gram(_dict): width W=%d above the compiled 13", W);
@@ -617,8 +520,6 @@ static int fill_lines_gram(int32_t fill_mode, int32_t n, int32_t line_begin, int
   SPAI_CHECK_ARG(gram_dtype == SPAI_DTYPE_F64 || gram_dtype == SPAI_DTYPE_F32, "spai_fill_lines_gram(_dict): gram dtype %d",
                  gram_dtype);
   const bool g32 = gram_dtype == SPAI_DTYPE_F32;
-  const int32_t nparts = (nl + kNT - 1) / kNT;
-  SPAI_CHECK_ARG(workspace_bytes >= sizeof(double) * (size_t)nparts * B, "spai_fill_lines_gram(_dict): workspace too small");
   double* partials = static_cast<double*>(workspace);
   const uint32_t* rm = removed;
   const int32_t wb = word_base;

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "spai_device.h"
+#include "spai_fill.h"
 #include "spai_status.h"
 #include "spai_timer.h"
 
@@ -44,19 +45,6 @@ constexpr int kQTabW = 5;     // widths whose (entry, mask) solutions are tabled
 // whole 16-byte pieces (float M, W = 5: 32 bytes)
 template <int W, typename TM>
 __host__ __device__ constexpr int qr_rec_bytes() { return ((W * (int)sizeof(TM) + 7) / 8 * 8 + 8 + 15) / 16 * 16; }
-
-// Sum over the L lanes of a group (L = 4, 8, 16, 32 consecutive lanes), valid on every lane of
-// the group with identical bits (each step adds a commutative pair).
-template <int L>
-__device__ __forceinline__ double group_sum(double v) {
-  v += dpp_d<0xB1, 0xf>(v);  // quad_perm [1, 0, 3, 2]
-  v += dpp_d<0x4E, 0xf>(v);  // quad_perm [2, 3, 0, 1]
-  if constexpr (L >= 8) v += dpp_d<0x141, 0xf>(v);  // row_half_mirror: quad 0 <-> quad 1
-  if constexpr (L >= 16) v += dpp_d<0x140, 0xf>(v);  // row_mirror: half-row 0 <-> 1
-  if constexpr (L >= 32) v += __shfl_xor(v, 16, kWave);
-  static_assert(L == 4 || L == 8 || L == 16 || L == 32, "group size");
-  return v;
-}
 
 // Union size of the rows the slots' A lines touch, per line (max over the lines -> *out).
 template <int W, int WA>
@@ -94,12 +82,6 @@ __global__ __launch_bounds__(kQNT) void k_qr_rows(int32_t n, int32_t wrt, const 
 #pragma unroll
   for (int o = 2; o < kWave; o <<= 1) rows = max(rows, (int)__shfl_xor(rows, o, kWave));
   if ((threadIdx.x & 63) == 0 && rows > 0) atomicMax(out, rows);
-}
-
-// 1/x to ~1 ulp: hardware reciprocal + one Newton step (x finite, non-zero)
-__device__ __forceinline__ double qr_rcp(double x) {
-  const double r = __builtin_amdgcn_rcp(x);
-  return fma(r, fma(-x, r, 1.0), r);
 }
 
 // A group lives inside one wavefront, and a wave's LDS instructions execute in order: a hand-off
@@ -145,9 +127,7 @@ __host__ __device__ constexpr int qr_group_stride() {  // in elements of TA
 }
 __host__ __device__ constexpr int odd_up(int x) { return x | 1; }
 
-#ifndef QR_WPE
-#define QR_WPE 2  // waves per SIMD of the 5-wide fill instances (175 VGPRs: 2 is what they reach)
-#endif
+constexpr int kQrWpe = 2;  // waves per SIMD of the 5-wide fill instances (175 VGPRs: 2 is what they reach)
 
 // LDS of the per-line factorisation (phase 1) for NT / L groups of L lanes.
 template <int W, int WA, int L, int RPL, int NT, typename TA>
@@ -250,7 +230,7 @@ __device__ __forceinline__ void qr_factor_line(QrStage<W, WA, L, RPL, NT, TA>& S
     const double sig = group_sum<L>(s1), xkk = group_sum<L>(xk);
     const double sq = sqrt(sig);
     const double alpha = xkk >= 0.0 ? -sq : sq;
-    const double tau = sig > 0.0 ? qr_rcp(sig - alpha * xkk) : 0.0;  // H = I - tau v v^T
+    const double tau = sig > 0.0 ? rcp_newton(sig - alpha * xkk) : 0.0;  // H = I - tau v v^T
     double v[RPL];
 #pragma unroll
     for (int i = 0; i < RPL; ++i) {
@@ -290,13 +270,6 @@ __device__ __forceinline__ void qr_factor_line(QrStage<W, WA, L, RPL, NT, TA>& S
 #undef SD
 }
 
-// 1/sqrt(t) to ~1 ulp: hardware reciprocal square root + one Newton step (t > 0, normal)
-__device__ __forceinline__ double qr_rsq(double t) {
-  const double r = __builtin_amdgcn_rsq(t);
-  const double e = fma(-t * r, r, 1.0);  // 1 - t r^2
-  return fma(0.5 * r, e, r);
-}
-
 // Phase 2 for one (line, sample) on ONE lane: min ||R_J m - c|| over the kept columns J of the
 // line's full-block R (R_J = Q^T D_J has the singular values of A[I, J], so the small problem
 // keeps the QR's accuracy: no normal equations).  The pivot of a kept column p stays in row p:
@@ -317,7 +290,7 @@ __device__ __forceinline__ double qr_masked_solve(double (&Rm)[W][W], double (&c
   {  // column 0 has no rows above it: its reflection would only flip row 0's sign (skipped)
     const double x0 = Rm[0][0];
     piv[0] = keep[0] && x0 * x0 > thr[0];
-    rd[0] = piv[0] ? qr_rcp(x0) : 0.0;
+    rd[0] = piv[0] ? rcp_newton(x0) : 0.0;
   }
 #pragma unroll
   for (int p = 1; p < W; ++p) {
@@ -330,10 +303,10 @@ __device__ __forceinline__ double qr_masked_solve(double (&Rm)[W][W], double (&c
       sig = fma(v[i], v[i], sig);
     }
     piv[p] = keep[p] && sig > thr[p];  // |R_pp| after the reflection > 1e-12 ||D[:, p]||
-    const double rs = qr_rsq(piv[p] ? sig : 1.0);
+    const double rs = rsq_newton(piv[p] ? sig : 1.0);
     const double sq = sig * rs;                                 // sqrt(sig)
     const double alpha = __builtin_copysign(sq, -xp);           // the new R_pp (sign opposite to x_p)
-    const double tau = piv[p] ? qr_rcp(fma(sq, __builtin_fabs(xp), sig)) : 0.0;  // 1 / (sig - alpha x_p)
+    const double tau = piv[p] ? rcp_newton(fma(sq, __builtin_fabs(xp), sig)) : 0.0;  // 1 / (sig - alpha x_p)
     v[p] = xp - alpha;
     rd[p] = piv[p] ? __builtin_copysign(rs, -xp) : 0.0;         // 1 / alpha
 #pragma unroll
@@ -364,7 +337,7 @@ __device__ __forceinline__ double qr_masked_solve(double (&Rm)[W][W], double (&c
 
 // The fused fill: phase 1 and phase 2 in one launch, A read every call (no cache).
 template <int W, int WA, int L, int RPL, int NT, typename TA, typename TM>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? QR_WPE : 2))) void k_qr_fill(int32_t n, int32_t line_begin, int32_t line_end, int32_t wrt,
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? kQrWpe : 2))) void k_qr_fill(int32_t n, int32_t line_begin, int32_t line_end, int32_t wrt,
                                                   const int32_t* __restrict__ pat_idx,
                                                   const int32_t* __restrict__ pat_act, int32_t wart,
                                                   const int32_t* __restrict__ a_idx, const TA* __restrict__ a_val,
@@ -489,14 +462,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void k_
 // back-substitution (qr_masked_solve), M staged through LDS and written with 16-byte `nt` buffer
 // stores, the line residuals summed per sample in a fixed order (the k_gram_fill partial layout:
 // 256-line blocks, so 256-line-aligned shards sum to one launch's bits).
-#ifndef QRS_WPE
-#define QRS_WPE 4
-#endif
+constexpr int kQrsWpe = 4;  // waves per SIMD asked of the 5-wide solve
 // kDict: rcache is the cache's dictionary (spai_qr_cache_dict: its distinct entries, NQ doubles
 // each, contiguous) and line_entry[j] names line j's entry; else the full cache, 64 lines
 // interleaved per entry value (coalesced).
 template <int W, typename TM, bool kDict>
-__global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? QRS_WPE : (W <= 7 ? 2 : 1)))) void k_qr_solve(
+__global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? kQrsWpe : (W <= 7 ? 2 : 1)))) void k_qr_solve(
     int32_t line_begin, int32_t line_end, int32_t wrt, const int32_t* __restrict__ pat_act,
     const double* __restrict__ rcache, const int32_t* __restrict__ line_entry, int32_t B,
     const uint32_t* __restrict__ removed, int32_t words, int32_t word_base, TM* __restrict__ m_out,
@@ -504,11 +475,7 @@ __global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? Q
   constexpr int T = W * (W + 1) / 2, NQ = qr_cache_q(W);
   static_assert(kQNT == kQLines, "one thread per line of a 256-line block");
   __shared__ double s_r2[kQChunk][kQNT];
-#ifndef QRS_WAVE_M
   __shared__ __attribute__((aligned(16))) TM s_m[2][kQNT * W];
-#else
-  __shared__ __attribute__((aligned(16))) TM s_m[1][kQNT * W];  // per-wave regions
-#endif
   // W > 7 (13-wide lines): the line's 91-value R is not held across the samples (with the working
   // copy it would take ~370 registers) but re-read per sample from the cache (its dictionary: L1/L2)
   constexpr bool kHold = W <= 7;
@@ -522,7 +489,7 @@ __global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? Q
   const int nvl = min(kQNT, line_end - (line_begin + lb * kQNT));
 
   int act[W];
-  {
+  {  // (load_line_acts written out: through the helper the 13-wide fp64 instances take two AGPRs more)
     int av[W];  // every load issued before any is used
 #pragma unroll
     for (int p = 0; p < W; ++p) av[p] = pat_act[(int64_t)jj * wrt + min(p, wrt - 1)];
@@ -552,7 +519,7 @@ __global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? Q
     thf[p] = (float)(1e-24 * s);  // (0 only below 1e-21: the floor then drops exact zeros only)
   }
   // bitmap word offset of a slot (recomputed where used: no registers held across the samples)
-  auto wofs = [&](int p) { return act[p] >= 0 ? (act[p] >> 5) - word_base : 0; };
+  auto wofs = [&](int p) { return slot_word(act[p], word_base); };
   uint32_t wd[W];  // the slots' bitmap words of the next sample are loaded while the current one is solved
 #pragma unroll
   for (int p = 0; p < W; ++p) wd[p] = removed[wofs(p)];
@@ -560,7 +527,7 @@ __global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? Q
   for (int b = 0; b < B; ++b) {
     bool keep[W];
 #pragma unroll
-    for (int p = 0; p < W; ++p) keep[p] = act[p] >= 0 && !((wd[p] >> (act[p] & 31)) & 1u);
+    for (int p = 0; p < W; ++p) keep[p] = slot_kept(act[p], wd[p]);
     if (b + 1 < B) {
       const uint32_t* rn = removed + (int64_t)(b + 1) * words;
 #pragma unroll
@@ -595,55 +562,11 @@ __global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(W <= 5 ? Q
     }
     const double rs = qr_masked_solve<W>(Rm, c, tail, thr, keep, m);
     s_r2[b % kQChunk][t] = valid ? rs : 0.0;
-#ifdef QRS_DIRECT  // A/B: M stored from the registers (no LDS staging, no barrier per sample)
-    if (m_out != nullptr && valid) {
-      TM* dst = m_out + ((int64_t)b * nloc + (j - line_begin)) * wrt;
-#pragma unroll
-      for (int p = 0; p < W; ++p)
-        if (p < wrt) nt_store(dst + p, (TM)m[p]);
-    }
-#else
-#ifndef QRS_WAVE_M  // M staged per block; QRS_WAVE_M (A/B): per wave, no block barrier per sample —
-                    // 6 VGPRs spilled at 128, 0.127 vs 0.106 ms at C4 (the Gram fills gain from it)
-    {  // M (no branch on m_out: store_m_block drops every store when it is null)
-      TM* sm = s_m[b & 1];
-      if (valid) {
-#pragma unroll
-        for (int p = 0; p < W; ++p)
-          if (p < wrt) sm[t * wrt + p] = (TM)m[p];
-      }
-      __syncthreads();
-      store_m_block<kQNT, W, TM>(m_out ? m_out + ((int64_t)b * nloc + (int64_t)lb * kQNT) * wrt : nullptr, sm,
-                                 nvl * wrt);
-    }
-#else
-    {  // M staged per WAVE (its 64 lines are one contiguous run of M): no block barrier per sample
-      const int wv = __builtin_amdgcn_readfirstlane(wave);  // wave-uniform: scalar offsets
-      TM* sm = s_m[0] + wv * 64 * W;
-      if (valid) {
-#pragma unroll
-        for (int p = 0; p < W; ++p)
-          if (p < wrt) sm[lane * wrt + p] = (TM)m[p];
-      }
-      __builtin_amdgcn_wave_barrier();
-      const int nw = min(max(nvl - wv * 64, 0), 64);
-      store_m_block<64, W, TM>(m_out ? m_out + ((int64_t)b * nloc + (int64_t)lb * kQNT + wv * 64) * wrt : nullptr,
-                               sm, nw * wrt, lane);
-      __builtin_amdgcn_wave_barrier();
-    }
-#endif
-#endif
+    // M staged per block (stage_m_block says why not per wave here)
+    stage_m_block<kQNT, W, TM>(s_m, m, valid, wrt, nvl, m_out, b, nloc, lb);
     if (b % kQChunk == kQChunk - 1 || b == B - 1) {  // the chunk's fixed-order block sums
       const int c0b = b - b % kQChunk, nb = b - c0b + 1;
-      __syncthreads();
-      for (int u = wave; u < nb; u += kQNT / 64) {
-        double acc = 0.0;
-#pragma unroll
-        for (int q = 0; q < kQNT / 64; ++q) acc += s_r2[u][q * 64 + lane];
-        acc = wave_sum(acc);
-        if (lane == 0) partials[(int64_t)(c0b + u) * gridDim.x + lb] = acc;
-      }
-      __syncthreads();
+      chunk_block_sums<kQNT>(s_r2, lane, wave, nb, c0b, partials, lb);
     }
   }
 }
@@ -691,11 +614,9 @@ __global__ __launch_bounds__(kQNT) void k_qr_table(int32_t entries, const double
 // is stored).  No solve and no per-line R or Q^T e held, so more blocks per CU than k_qr_solve; M
 // staged per block and stored, and the residual sums formed, exactly as k_qr_solve does (the same
 // bits as solving every (line, sample) on its own lane).
-#ifndef QR_LOOKUP_WPE
-#define QR_LOOKUP_WPE 6
-#endif
+constexpr int kQrLookupWpe = 6;
 template <int W, typename TM>
-__global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(QR_LOOKUP_WPE))) void k_qr_lookup(
+__global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(kQrLookupWpe))) void k_qr_lookup(
     int32_t line_begin, int32_t line_end, int32_t wrt, const int32_t* __restrict__ pat_act,
     const int32_t* __restrict__ line_entry, int32_t B, const uint32_t* __restrict__ removed, int32_t words,
     int32_t word_base, TM* __restrict__ m_out, double* __restrict__ partials, const char* __restrict__ mtab) {
@@ -711,19 +632,13 @@ __global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(QR_LOOKUP_
   const int jj = valid ? j : line_begin;  // clamped: loads stay in bounds
   const int nvl = min(kQNT, line_end - (line_begin + lb * kQNT));
   int act[W];
-  {
-    int av[W];
-#pragma unroll
-    for (int p = 0; p < W; ++p) av[p] = pat_act[(int64_t)jj * wrt + min(p, wrt - 1)];
-#pragma unroll
-    for (int p = 0; p < W; ++p) act[p] = (valid && p < wrt) ? av[p] : -1;
-  }
+  load_line_acts<W>(pat_act, jj, wrt, valid, act);
   const u4t* tab = reinterpret_cast<const u4t*>(mtab) + (int64_t)line_entry[jj] * kMasks * kRW;
-  auto wofs = [&](int p) { return act[p] >= 0 ? (act[p] >> 5) - word_base : 0; };
+  auto wofs = [&](int p) { return slot_word(act[p], word_base); };
   auto mask_of = [&](const uint32_t (&w)[W]) {
     int mt = 0;
 #pragma unroll
-    for (int p = 0; p < W; ++p) mt |= (int)(act[p] >= 0 && !((w[p] >> (act[p] & 31)) & 1u)) << p;
+    for (int p = 0; p < W; ++p) mt |= (int)slot_kept(act[p], w[p]) << p;
     return mt;
   };
   // per group of kG samples: their W * kG bitmap words in flight together, then their kG records
@@ -761,94 +676,43 @@ __global__ __launch_bounds__(kQNT) __attribute__((amdgpu_waves_per_eu(QR_LOOKUP_
             const TM* mv = reinterpret_cast<const TM*>(&rc[i][0]);
             const double rs = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(&rc[i][0]) + kRec - 8);
             s_r2[g0 + i][t] = valid ? rs : 0.0;
-            TM* sm = s_m[b & 1];
-            if (valid) {
-#pragma unroll
-              for (int p = 0; p < W; ++p)
-                if (p < wrt) sm[t * wrt + p] = mv[p];
-            }
-            __syncthreads();
-            store_m_block<kQNT, W, TM>(m_out ? m_out + ((int64_t)b * nloc + (int64_t)lb * kQNT) * wrt : nullptr, sm,
-                                       nvl * wrt);
+            stage_m_block<kQNT, W, TM>(s_m, mv, valid, wrt, nvl, m_out, b, nloc, lb);
           }
         }
       }
     }
-    // the chunk's fixed-order block sums (k_qr_solve's)
-    __syncthreads();
-    for (int u = wave; u < nb; u += kQNT / 64) {
-      double acc = 0.0;
-#pragma unroll
-      for (int q = 0; q < kQNT / 64; ++q) acc += s_r2[u][q * 64 + lane];
-      acc = wave_sum(acc);
-      if (lane == 0) partials[(int64_t)(b0 + u) * gridDim.x + lb] = acc;
-    }
-    __syncthreads();
+    chunk_block_sums<kQNT>(s_r2, lane, wave, nb, b0, partials, lb);  // (k_qr_solve's)
   }
 }
 
-// (W class, A width class, rows) -> instance
-template <int W, int WA, int L, int RPL, int NT, typename TM>
-hipError_t launch_qr(bool a32, int32_t n, int32_t lb, int32_t le, int32_t wrt, const int32_t* pi, const int32_t* pa,
+// THE (width class, rows) -> <W, WA, L, RPL, NT> instance table: the fused fill and the R cache
+// build both go through it (they must agree: the cached solve equals the fused one bit for bit).
+template <int W_, int WA_, int L_, int RPL_, int NT_>
+struct QrInstance {
+  static constexpr int W = W_, WA = WA_, L = L_, RPL = RPL_, NT = NT_;
+};
+template <typename F>
+hipError_t with_qr_instance(int wc, int rows, F&& f) {
+  if (wc == 5) return rows <= 16 ? f(QrInstance<5, 5, 4, 4, 256>{}) : f(QrInstance<5, 5, 8, 4, 256>{});
+  if (wc == 7) return rows <= 32 ? f(QrInstance<7, 7, 8, 4, 256>{}) : f(QrInstance<7, 7, 16, 4, 128>{});
+  return rows <= 64 ? f(QrInstance<13, 7, 16, 4, 128>{}) : f(QrInstance<13, 7, 32, 3, 128>{});
+}
+
+template <typename I, typename TA, typename TM>
+hipError_t launch_qr(I, int32_t n, int32_t lb, int32_t le, int32_t wrt, const int32_t* pi, const int32_t* pa,
                      int32_t wart, const int32_t* ai, const void* av, int32_t B, const uint32_t* rm, int32_t words,
                      int32_t wb, void* mo, double* partials, int32_t nparts, hipStream_t s) {
-  if (a32)
-    k_qr_fill<W, WA, L, RPL, NT, float, TM><<<nparts, NT, 0, s>>>(n, lb, le, wrt, pi, pa, wart, ai,
-                                                                static_cast<const float*>(av), B, rm, words, wb,
-                                                                static_cast<TM*>(mo), partials);
-  else
-    k_qr_fill<W, WA, L, RPL, NT, double, TM><<<nparts, NT, 0, s>>>(n, lb, le, wrt, pi, pa, wart, ai,
-                                                                 static_cast<const double*>(av), B, rm, words, wb,
-                                                                 static_cast<TM*>(mo), partials);
+  k_qr_fill<I::W, I::WA, I::L, I::RPL, I::NT, TA, TM><<<nparts, I::NT, 0, s>>>(
+      n, lb, le, wrt, pi, pa, wart, ai, static_cast<const TA*>(av), B, rm, words, wb, static_cast<TM*>(mo), partials);
   return hipGetLastError();
 }
 
-template <typename TM>
-hipError_t dispatch_qr(int wc, int rows, bool a32, int32_t n, int32_t lb, int32_t le, int32_t wrt, const int32_t* pi,
-                       const int32_t* pa, int32_t wart, const int32_t* ai, const void* av, int32_t B,
-                       const uint32_t* rm, int32_t words, int32_t wb, void* mo, double* partials, int32_t nparts,
-                       hipStream_t s) {
-#define SPAI_QR_ARGS a32, n, lb, le, wrt, pi, pa, wart, ai, av, B, rm, words, wb, mo, partials, nparts, s
-  if (wc == 5) {
-    if (rows <= 16) return launch_qr<5, 5, 4, 4, 256, TM>(SPAI_QR_ARGS);
-    return launch_qr<5, 5, 8, 4, 256, TM>(SPAI_QR_ARGS);
-  }
-  if (wc == 7) {
-    if (rows <= 32) return launch_qr<7, 7, 8, 4, 256, TM>(SPAI_QR_ARGS);
-    return launch_qr<7, 7, 16, 4, 128, TM>(SPAI_QR_ARGS);
-  }
-  if (rows <= 64) return launch_qr<13, 7, 16, 4, 128, TM>(SPAI_QR_ARGS);
-  return launch_qr<13, 7, 32, 3, 128, TM>(SPAI_QR_ARGS);
-#undef SPAI_QR_ARGS
-}
-
-// the R cache build: the same (W class, rows) -> instance choice as the fused fill
-template <int W, int WA, int L, int RPL, int NT>
-hipError_t launch_factor(bool a32, int32_t n, int32_t wrt, const int32_t* pi, const int32_t* pa, int32_t wart,
+template <typename I, typename TA>
+hipError_t launch_factor(I, int32_t n, int32_t wrt, const int32_t* pi, const int32_t* pa, int32_t wart,
                          const int32_t* ai, const void* av, double* rc, hipStream_t s) {
-  const int grid = (n + kQLines - 1) / kQLines;
-  if (a32)
-    k_qr_factor<W, WA, L, RPL, NT, float><<<grid, NT, 0, s>>>(n, wrt, pi, pa, wart, ai, static_cast<const float*>(av),
-                                                             rc);
-  else
-    k_qr_factor<W, WA, L, RPL, NT, double><<<grid, NT, 0, s>>>(n, wrt, pi, pa, wart, ai,
-                                                              static_cast<const double*>(av), rc);
+  k_qr_factor<I::W, I::WA, I::L, I::RPL, I::NT, TA><<<(n + kQLines - 1) / kQLines, I::NT, 0, s>>>(
+      n, wrt, pi, pa, wart, ai, static_cast<const TA*>(av), rc);
   return hipGetLastError();
-}
-hipError_t dispatch_factor(int wc, int rows, bool a32, int32_t n, int32_t wrt, const int32_t* pi, const int32_t* pa,
-                           int32_t wart, const int32_t* ai, const void* av, double* rc, hipStream_t s) {
-#define SPAI_QF_ARGS a32, n, wrt, pi, pa, wart, ai, av, rc, s
-  if (wc == 5) {
-    if (rows <= 16) return launch_factor<5, 5, 4, 4, 256>(SPAI_QF_ARGS);
-    return launch_factor<5, 5, 8, 4, 256>(SPAI_QF_ARGS);
-  }
-  if (wc == 7) {
-    if (rows <= 32) return launch_factor<7, 7, 8, 4, 256>(SPAI_QF_ARGS);
-    return launch_factor<7, 7, 16, 4, 128>(SPAI_QF_ARGS);
-  }
-  if (rows <= 64) return launch_factor<13, 7, 16, 4, 128>(SPAI_QF_ARGS);
-  return launch_factor<13, 7, 32, 3, 128>(SPAI_QF_ARGS);
-#undef SPAI_QF_ARGS
 }
 
 template <int W, typename TM>
@@ -923,41 +787,36 @@ extern "C" int spai_fill_lines_qr(int32_t n, int32_t line_begin, int32_t line_en
                                   int32_t a_dtype, int32_t max_rows, int32_t B, const uint32_t* removed, int32_t words,
                                   int32_t word_base, void* m_out, int32_t m_dtype, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  SPAI_CHECK_ARG(m_dtype == SPAI_DTYPE_F32 || m_dtype == SPAI_DTYPE_F64, "spai_fill_lines_qr: bad m_dtype");
   SPAI_CHECK_ARG(a_dtype == SPAI_DTYPE_F32 || a_dtype == SPAI_DTYPE_F64, "spai_fill_lines_qr: bad a_dtype");
-  SPAI_CHECK_ARG(n >= 1 && line_begin >= 0 && line_end >= line_begin && line_end <= n && W >= 1 && WA >= 1 &&
-                     B >= 1 && words >= 1 && word_base >= 0 && max_rows >= 0,
-                 "spai_fill_lines_qr: bad shape");
-  SPAI_CHECK_ARG(workspace != nullptr, "spai_fill_lines_qr: null workspace");
-  const int32_t nl = line_end - line_begin;
-  if (nl == 0) return SPAI_OK;
-  SPAI_CHECK_ARG(pat_idx && pat_act && a_idx && a_val && removed, "spai_fill_lines_qr: null input");
+  int32_t nparts;
+  const int st = check_fill_lines("spai_fill_lines_qr", n, line_begin, line_end, W, B, words, word_base,
+                                  WA >= 1 && max_rows >= 0, m_dtype, workspace, workspace_bytes,
+                                  pat_idx && pat_act && a_idx && a_val && removed, &nparts);
+  if (st != SPAI_OK || nparts == 0) return st;
   const int wc = qr_class(W, WA);
   if (wc == 0 || max_rows > qr_rows_cap(wc)) {
     set_error("spai_fill_lines_qr: widths W=%d WA=%d / %d rows above the compiled 13 / 7 / %d", W, WA, max_rows,
               wc ? qr_rows_cap(wc) : 0);
     return SPAI_ERR_UNSUPPORTED;
   }
-  const int32_t nparts = (nl + kQLines - 1) / kQLines;
-  SPAI_CHECK_ARG(workspace_bytes >= sizeof(double) * (size_t)nparts * B, "spai_fill_lines_qr: workspace too small");
   double* partials = static_cast<double*>(workspace);
   hipStream_t s = (hipStream_t)stream;
-  const bool a32 = a_dtype == SPAI_DTYPE_F32;
-  const hipError_t e =
-      m_dtype == SPAI_DTYPE_F64
-          ? dispatch_qr<double>(wc, max_rows, a32, n, line_begin, line_end, W, pat_idx, pat_act, WA, a_idx, a_val, B,
-                                removed, words, word_base, m_out, partials, nparts, s)
-          : dispatch_qr<float>(wc, max_rows, a32, n, line_begin, line_end, W, pat_idx, pat_act, WA, a_idx, a_val, B,
-                               removed, words, word_base, m_out, partials, nparts, s);
-  SPAI_CHECK_HIP(e);
+  const bool a32 = a_dtype == SPAI_DTYPE_F32, f64 = m_dtype == SPAI_DTYPE_F64;
+  SPAI_CHECK_HIP(with_qr_instance(wc, max_rows, [&](auto inst) {
+    auto launch = [&](auto ta, auto tm) {
+      return launch_qr<decltype(inst), decltype(ta), decltype(tm)>(inst, n, line_begin, line_end, W, pat_idx, pat_act,
+                                                                   WA, a_idx, a_val, B, removed, words, word_base,
+                                                                   m_out, partials, nparts, s);
+    };
+    return a32 ? (f64 ? launch(float{}, double{}) : launch(float{}, float{}))
+               : (f64 ? launch(double{}, double{}) : launch(double{}, float{}));
+  }));
   return SPAI_OK;
 }
 
 // ---- the R cache (phase 1 once per env) and the per-rollout solve from it
-static int qr_cache_class(int32_t W, int32_t WA) { return qr_class(W, WA); }
-
 extern "C" size_t spai_qr_cache_bytes(int32_t n, int32_t W, int32_t WA) {
-  const int wc = qr_cache_class(W, WA);
+  const int wc = qr_class(W, WA);
   if (n <= 0 || wc == 0) return 0;
   return sizeof(double) * (size_t)qr_cache_q(wc) * (size_t)((n + 63) / 64 * 64);
 }
@@ -968,15 +827,19 @@ extern "C" int spai_qr_factor(int32_t n, int32_t W, const int32_t* pat_idx, cons
   SPAI_CHECK_ARG(n >= 1 && W >= 1 && WA >= 1 && max_rows >= 0 && pat_idx && pat_act && a_idx && a_val && rcache,
                  "spai_qr_factor: bad arguments");
   SPAI_CHECK_ARG(a_dtype == SPAI_DTYPE_F32 || a_dtype == SPAI_DTYPE_F64, "spai_qr_factor: bad a_dtype");
-  const int wc = qr_cache_class(W, WA);
+  const int wc = qr_class(W, WA);
   if (wc == 0 || max_rows > qr_rows_cap(wc)) {
     set_error("spai_qr_factor: widths W=%d WA=%d / %d rows above the compiled 13 / 7 / %d", W, WA, max_rows,
               wc ? qr_rows_cap(wc) : 0);
     return SPAI_ERR_UNSUPPORTED;
   }
   SPAI_CHECK_ARG(rcache_bytes >= spai_qr_cache_bytes(n, W, WA), "spai_qr_factor: rcache too small");
-  SPAI_CHECK_HIP(dispatch_factor(wc, max_rows, a_dtype == SPAI_DTYPE_F32, n, W, pat_idx, pat_act, WA, a_idx, a_val,
-                                 rcache, (hipStream_t)stream));
+  hipStream_t s = (hipStream_t)stream;
+  SPAI_CHECK_HIP(with_qr_instance(wc, max_rows, [&](auto inst) {
+    using I = decltype(inst);
+    return a_dtype == SPAI_DTYPE_F32 ? launch_factor<I, float>(inst, n, W, pat_idx, pat_act, WA, a_idx, a_val, rcache, s)
+                                     : launch_factor<I, double>(inst, n, W, pat_idx, pat_act, WA, a_idx, a_val, rcache, s);
+  }));
   return SPAI_OK;
 }
 
@@ -985,24 +848,17 @@ extern "C" int spai_fill_lines_qr_cached(int32_t n, int32_t line_begin, int32_t 
                                          int32_t entries, int32_t B, const uint32_t* removed, int32_t words,
                                          int32_t word_base, void* m_out, int32_t m_dtype, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-  SPAI_CHECK_ARG(m_dtype == SPAI_DTYPE_F32 || m_dtype == SPAI_DTYPE_F64, "spai_fill_lines_qr_cached: bad m_dtype");
-  SPAI_CHECK_ARG(n >= 1 && line_begin >= 0 && line_end >= line_begin && line_end <= n && W >= 1 && WA >= 1 &&
-                     B >= 1 && words >= 1 && word_base >= 0,
-                 "spai_fill_lines_qr_cached: bad shape");
-  SPAI_CHECK_ARG(workspace != nullptr, "spai_fill_lines_qr_cached: null workspace");
-  const int32_t nl = line_end - line_begin;
-  if (nl == 0) return SPAI_OK;
-  SPAI_CHECK_ARG(pat_act && rcache && removed, "spai_fill_lines_qr_cached: null input");
-  const int wc = qr_cache_class(W, WA);
+  int32_t nparts;
+  const int st = check_fill_lines("spai_fill_lines_qr_cached", n, line_begin, line_end, W, B, words, word_base, WA >= 1,
+                                  m_dtype, workspace, workspace_bytes, pat_act && rcache && removed, &nparts);
+  if (st != SPAI_OK || nparts == 0) return st;
+  const int wc = qr_class(W, WA);
   if (wc != 5 && wc != 7 && wc != 13) {
     set_error("spai_fill_lines_qr_cached: width class %d (W=%d WA=%d): the cached solve is compiled for 5, 7 and 13",
               wc, W, WA);
     return SPAI_ERR_UNSUPPORTED;
   }
   SPAI_CHECK_ARG(!line_entry || entries >= 1, "spai_fill_lines_qr_cached: a dictionary needs entries >= 1");
-  const int32_t nparts = (nl + kQNT - 1) / kQNT;
-  SPAI_CHECK_ARG(workspace_bytes >= sizeof(double) * (size_t)nparts * B,
-                 "spai_fill_lines_qr_cached: workspace too small");
   double* partials = static_cast<double*>(workspace);
   // the (entry, mask) table after the partials, when the dictionary is small and the workspace has room
   double* mtab = nullptr;

@@ -28,6 +28,7 @@
 #include <climits>
 
 #include "spai_device.h"
+#include "spai_fill.h"
 #include "spai_status.h"
 
 namespace spai {
@@ -41,27 +42,6 @@ constexpr int kWChunk = 64;     // samples whose block sums are in LDS at once (
 
 __host__ __device__ constexpr int qrw_nq(int W) { return W * (W + 1) / 2 + W + 1; }
 __host__ __device__ constexpr int qrw_row(int i, int W) { return i * W - i * (i - 1) / 2; }  // offset of R[i][i]
-
-// 1/x and 1/sqrt(t) to ~1 ulp (qr.hip's: hardware estimate + one Newton step)
-__device__ __forceinline__ double qrw_rcp(double x) {
-  const double r = __builtin_amdgcn_rcp(x);
-  return fma(r, fma(-x, r, 1.0), r);
-}
-__device__ __forceinline__ double qrw_rsq(double t) {
-  const double r = __builtin_amdgcn_rsq(t);
-  const double e = fma(-t * r, r, 1.0);
-  return fma(0.5 * r, e, r);
-}
-
-// Sum over the 32 lanes of a half-wave, identical bits on every lane of the half (qr.hip's group_sum<32>).
-__device__ __forceinline__ double half_sum(double v) {
-  v += dpp_d<0xB1, 0xf>(v);   // quad_perm [1, 0, 3, 2]
-  v += dpp_d<0x4E, 0xf>(v);   // quad_perm [2, 3, 0, 1]
-  v += dpp_d<0x141, 0xf>(v);  // row_half_mirror
-  v += dpp_d<0x140, 0xf>(v);  // row_mirror
-  v += __shfl_xor(v, 16, kWave);
-  return v;
-}
 
 __device__ __forceinline__ int wave_min_i(int v) {
 #pragma unroll
@@ -208,7 +188,7 @@ __global__ __launch_bounds__(NT) void k_qrw_factor(int32_t n, int32_t wrt, const
       const double sig = sx[0], xkk = sx[1];
       const double sq = sqrt(sig);
       const double alpha = xkk >= 0.0 ? -sq : sq;
-      const double tau = sig > 0.0 ? qrw_rcp(sig - alpha * xkk) : 0.0;  // H = I - tau v v^T
+      const double tau = sig > 0.0 ? rcp_newton(sig - alpha * xkk) : 0.0;  // H = I - tau v v^T
       const double v = t >= p ? d[p] - (t == p ? alpha : 0.0) : 0.0;
       double dot[kWW + 1];  // v . column q (q > p) at [q], v . rhs at [wrt]
 #pragma unroll
@@ -290,12 +270,13 @@ __global__ __launch_bounds__(kWNT) __attribute__((amdgpu_waves_per_eu(2))) void 
         thr = 1e-24 * s;
       }
       const int act = q < wrt ? pat_act[(int64_t)l * wrt + q] : -1;
-      const int wofs = act >= 0 ? (act >> 5) - word_base : 0;
+      const int wofs = slot_word(act, word_base);
 #pragma unroll 1
       for (int s0 = 0; s0 < nb; s0 += 2) {
         const int sl = min(s0 + half, nb - 1);  // an odd last pair: both halves solve the last sample
         const bool own = s0 + half < nb;
         const int b = b0 + sl;
+        // (slot_kept written out: the bitmap load stays under the act >= 0 test, as the registers were tuned)
         const bool keep = act >= 0 && !((removed[(int64_t)b * words + wofs] >> (act & 31)) & 1u);
         double x[kWW];
         {
@@ -318,7 +299,7 @@ __global__ __launch_bounds__(kWNT) __attribute__((amdgpu_waves_per_eu(2))) void 
         {  // column 0 has no rows above it: its reflection would only flip row 0's sign (skipped)
           const bool pv = (kh & 1u) && r00 * r00 > __shfl(thr, 0, 32);
           fm[0] = pv ? 0u : ~0u;
-          if (q == 0) rd = pv ? qrw_rcp(r00) : 0.0;
+          if (q == 0) rd = pv ? rcp_newton(r00) : 0.0;
         }
 #pragma unroll
         for (int p = 1; p < kWW; ++p) {
@@ -338,10 +319,10 @@ __global__ __launch_bounds__(kWNT) __attribute__((amdgpu_waves_per_eu(2))) void 
               sig = fma(v[i], v[i], sig);
             }
             const bool pv = ((kh >> p) & 1u) && sig > thp;  // |R_pp| after the reflection > 1e-12 ||D[:, p]||
-            const double rs = qrw_rsq(pv ? sig : 1.0);
+            const double rs = rsq_newton(pv ? sig : 1.0);
             const double sq = sig * rs;
             const double alpha = __builtin_copysign(sq, -xp);  // the new R_pp (sign opposite to x_p)
-            const double tau = pv ? qrw_rcp(fma(sq, __builtin_fabs(xp), sig)) : 0.0;  // 1 / (sig - alpha x_p)
+            const double tau = pv ? rcp_newton(fma(sq, __builtin_fabs(xp), sig)) : 0.0;  // 1 / (sig - alpha x_p)
             v[p] = xp - alpha;
             if (q == p) rd = pv ? __builtin_copysign(rs, -xp) : 0.0;  // 1 / alpha
             fm[p] = pv ? 0u : ~0u;
@@ -361,7 +342,7 @@ __global__ __launch_bounds__(kWNT) __attribute__((amdgpu_waves_per_eu(2))) void 
 #pragma unroll
         for (int p = kWW - 1; p >= 0; --p) {
           if (p < wrt) {
-            const double sum = half_sum(q == 0 ? x[p] : (q > p ? -x[p] * mq : 0.0));
+            const double sum = group_sum<32>(q == 0 ? x[p] : (q > p ? -x[p] * mq : 0.0));
             if (q == p) mq = sum * rd;  // 0 for a dropped slot
           }
         }
@@ -443,23 +424,16 @@ extern "C" int spai_fill_lines_qr_wide(int32_t n, int32_t line_begin, int32_t li
                                        const int32_t* pat_act, const double* rcache, size_t rcache_bytes, int32_t B,
                                        const uint32_t* removed, int32_t words, int32_t word_base, void* m_out,
                                        int32_t m_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  SPAI_CHECK_ARG(m_dtype == SPAI_DTYPE_F32 || m_dtype == SPAI_DTYPE_F64, "spai_fill_lines_qr_wide: bad m_dtype");
-  SPAI_CHECK_ARG(n >= 1 && line_begin >= 0 && line_end >= line_begin && line_end <= n && W >= 1 && B >= 1 &&
-                     words >= 1 && word_base >= 0,
-                 "spai_fill_lines_qr_wide: bad shape");
-  SPAI_CHECK_ARG(workspace != nullptr, "spai_fill_lines_qr_wide: null workspace");
-  const int32_t nl = line_end - line_begin;
-  if (nl == 0) return SPAI_OK;
-  SPAI_CHECK_ARG(pat_act && rcache && removed, "spai_fill_lines_qr_wide: null input");
+  int32_t nparts;
+  const int st = check_fill_lines("spai_fill_lines_qr_wide", n, line_begin, line_end, W, B, words, word_base, true,
+                                  m_dtype, workspace, workspace_bytes, pat_act && rcache && removed, &nparts);
+  if (st != SPAI_OK || nparts == 0) return st;
   if (W > kWW) {
     set_error("spai_fill_lines_qr_wide: width W=%d above the compiled %d (A width <= %d, row union <= %d)", W, kWW,
               kWW, kWRows);
     return SPAI_ERR_UNSUPPORTED;
   }
   SPAI_CHECK_ARG(rcache_bytes >= spai_qr_wide_cache_bytes(n, W), "spai_fill_lines_qr_wide: rcache too small");
-  const int32_t nparts = (nl + kWLines - 1) / kWLines;
-  SPAI_CHECK_ARG(workspace_bytes >= sizeof(double) * (size_t)nparts * B,
-                 "spai_fill_lines_qr_wide: workspace too small");
   double* partials = static_cast<double*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   if (m_dtype == SPAI_DTYPE_F64)

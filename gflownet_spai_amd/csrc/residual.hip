@@ -197,6 +197,35 @@ __device__ __forceinline__ double line_res2_any(const int (&k)[W], const double 
 #endif
 constexpr int kChunk = KCHUNK;
 
+// The chunk epilogue of the line kernels.  chunk_partials: thread i < nb adds sample i's NG group
+// sums sred[i][.] in order and writes partials[b0 + i][blk], between two barriers (the plain adds
+// of loaded values cannot be contracted).  chunk_wave_sums first forms those group sums as wave
+// sums (DPP, fixed association) of every lane's r2s[i].
+template <int C, int NG>
+__device__ __forceinline__ void chunk_partials(const double (&sred)[C][NG], int nb, int b0, int32_t nblk, int blk,
+                                               double* partials) {
+  __syncthreads();
+  if (threadIdx.x < nb) {
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < NG; ++u) s += sred[threadIdx.x][u];
+    partials[(int64_t)(b0 + threadIdx.x) * nblk + blk] = s;
+  }
+  __syncthreads();
+}
+template <int C>
+__device__ __forceinline__ void chunk_wave_sums(const double (&r2s)[C], int lane, int w, double (&sred)[C][kNT / 64],
+                                                int nb, int b0, int32_t nblk, int blk, double* partials) {
+#pragma unroll
+  for (int i = 0; i < C; ++i) {
+    if (i < nb) {
+      const double r2 = wave_sum_dpp(r2s[i]);
+      if (lane == 0) sred[i][w] = r2;
+    }
+  }
+  chunk_partials(sred, nb, b0, nblk, blk, partials);
+}
+
 template <int W, int WA, bool FULL, typename TA, typename TV>
 __device__ __forceinline__ void resid_shared_body(int32_t line_begin, int32_t line_end, int32_t wrt, int32_t wart,
                                                   int32_t B, int32_t nblk, const int32_t* __restrict__ m_idx,
@@ -297,21 +326,7 @@ __device__ __forceinline__ void resid_shared_body(int32_t line_begin, int32_t li
         }
       }
     }
-#pragma unroll
-    for (int i = 0; i < kChunk; ++i) {
-      if (i < nb) {
-        const double r2 = wave_sum_dpp(r2s[i]);
-        if (lane == 0) sred[i][w] = r2;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < nb) {
-      double s = 0.0;
-#pragma unroll
-      for (int u = 0; u < kNT / 64; ++u) s += sred[threadIdx.x][u];
-      partials[(int64_t)(b0 + threadIdx.x) * nblk + blk] = s;
-    }
-    __syncthreads();
+    chunk_wave_sums(r2s, lane, w, sred, nb, b0, nblk, blk, partials);
   }
 }
 
@@ -454,21 +469,7 @@ __device__ __forceinline__ void resid_wide_body(int32_t line_begin, int32_t line
         for (int u = 0; u < C; ++u) r2s[u] = u == i ? r2 : r2s[u];
       }
     }
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-      if (i < nb) {
-        const double r2 = wave_sum_dpp(r2s[i]);
-        if (lane == 0) sred[i][w] = r2;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < nb) {
-      double s = 0.0;
-#pragma unroll
-      for (int u = 0; u < kNT / 64; ++u) s += sred[threadIdx.x][u];
-      partials[(int64_t)(b0 + threadIdx.x) * nblk + blk] = s;
-    }
-    __syncthreads();
+    chunk_wave_sums(r2s, lane, w, sred, nb, b0, nblk, blk, partials);
   }
 }
 
@@ -637,21 +638,7 @@ __device__ __forceinline__ void resid_gram_body(int32_t line_begin, int32_t line
 #pragma unroll
       for (int u = 0; u < kChunk; ++u) r2s[u] = u == i ? r2 : r2s[u];
     }
-#pragma unroll
-    for (int i = 0; i < kChunk; ++i) {
-      if (i < nb) {
-        const double r2 = wave_sum_dpp(r2s[i]);
-        if (lane == 0) sred[i][w] = r2;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < nb) {
-      double s = 0.0;
-#pragma unroll
-      for (int u = 0; u < kNT / 64; ++u) s += sred[threadIdx.x][u];
-      partials[(int64_t)(b0 + threadIdx.x) * nblk + blk] = s;
-    }
-    __syncthreads();
+    chunk_wave_sums(r2s, lane, w, sred, nb, b0, nblk, blk, partials);
   }
 }
 
@@ -897,14 +884,7 @@ __device__ __forceinline__ void resid_row16_body(int32_t line_begin, int32_t lin
 #pragma unroll
       for (int i = 0; i < kRowC; ++i) sred[i][r] = tot[i];
     }
-    __syncthreads();
-    if (threadIdx.x < nb) {
-      double s = 0.0;
-#pragma unroll
-      for (int u = 0; u < kGroups; ++u) s = __dadd_rn(s, sred[threadIdx.x][u]);
-      partials[(int64_t)(b0 + threadIdx.x) * nblk + blk] = s;
-    }
-    __syncthreads();
+    chunk_partials(sred, nb, b0, nblk, blk, partials);
   }
 }
 
